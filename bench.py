@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- the headline metric of BASELINE.json on MI355X, and the reference's two timing tables.
 
-    python bench.py --gpus N --steps K --warmup W                    (the driver's contract)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]      (the driver's contract)
+    python bench.py --gpus N --steps K --warmup W --full                     (everything else below as well)
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one pass of the hot path over one batch of synthetic QPs that is already resident in HBM:
@@ -10,14 +11,20 @@ the measurement of SURVEY.md section 8d / prof-linear.py:110-118, device-synchro
 prof-linear.py:99.  Default workload = BASELINE.json configs[1] extended with the backward pass as its `metric`
 asks: batch=512, nz=100, nineq=100, neq=0, float64 (the dtype the 1e-4 parity gate holds in).
 
+A plain run does only what the headline needs: set-up, the untimed spin-up and the W warm-up steps, exactly K timed steps,
+the result line (`value`, `ms_per_step` = the timed region / K, `wall_s`).  --dump-outputs DIR then writes what the last
+timed step returned to its caller -- zhat and the gradients the step asks for (dp; dQ, dG with --shared; the all_gathered
+zhat at N > 1) -- as DIR/<name>.npy in the tensors' dtype; outputs beyond 48 MiB in all are cut to the same fixed, seeded
+sample of rows.  The inputs are seeded, so two builds can be compared output for output.
+
 Before the W warm-up steps the script runs --spin-up seconds (default 0.5) of the same step, untimed: the first GPU work of a
 fresh box runs ~7 % slower for its first few hundred steps (774 K against 831 K QPs/s, profiles/r05v_spin_up.txt); the timed
-region is exactly K steps either way (`untimed_spin_up_s` in the JSON line; --spin-up 0 turns it off).  So that rounds stay
-comparable the line also carries the number of the protocol of rounds 1-4 from the same process: W warm-up steps, then 20
-timed steps, BEFORE the spin-up (`first_20_steps_qps`), and where the wall time of the run went (`wall_s`).
+region is exactly K steps either way (`untimed_spin_up_s` in the JSON line; --spin-up 0 turns it off).  With --full, so that
+rounds stay comparable, the line also carries the number of the protocol of rounds 1-4 from the same process: W warm-up
+steps, then 20 timed steps, BEFORE the spin-up (`first_20_steps_qps`).
 
-QPX_FORCE_DIST=1 takes the N > 1 branch (RCCL process group, zhat all_gathered beside the backward, the C5 point) with
-WORLD_SIZE = 1: the collective code path on the one GPU of a box (tests/test_gpu_dist.py).
+QPX_FORCE_DIST=1 takes the N > 1 branch (RCCL process group, zhat all_gathered beside the backward; the C5 point with
+--full) with WORLD_SIZE = 1: the collective code path on the one GPU of a box (tests/test_gpu_dist.py).
 
 Multi-GPU (one process per GPU, RCCL):
   --config c2 (default)  every rank solves its own 512-QP shard and the ranks all_gather zhat (the only exchange
@@ -25,7 +32,9 @@ Multi-GPU (one process per GPU, RCCL):
   --config c5            BASELINE.json configs[4]: a FIXED global batch of 65 536 QPs (nz=nineq=64) split by
                          qpth_amd.dist.shard_bounds, zhat gathered                       => "scaling": "strong"
 
-The JSON line also carries
+With --full the JSON line also carries (behind the timed region; none of it changes `value` or `ms_per_step`)
+  ms_per_step_median_of_10_step_chunks, first_20_steps_qps
+  extra ......... N > 1: the C5 strong-scaling point; N = 1, default command: BASELINE.json's C3, C4 and C5 on one GPU
   roofline ...... the dominant kernel (the PDIPM loop): algorithmic flops and bytes per launch / the launch's
                   duration measured live with HIP events on the launch stream; `traffic` = HBM bytes per launch
                   from the PMC passes of scripts/gpu_check.sh, reported only if they were taken on THIS build
@@ -281,6 +290,22 @@ def side_config(dev, B, n, m, q, steps, warmup, on_device=False):
             "ms_per_step": dt / steps * 1e3, "steps": steps, "warmup": warmup}
 
 
+DUMP_MAX_BYTES = 48 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: each tensor of `outputs` as out_dir/<name>.npy in its own dtype (float32 / float64).  Over
+    DUMP_MAX_BYTES in all, every tensor keeps the same share of its rows, picked by a fixed seed (C5: 65 536 QPs)."""
+    arrays = {k: v.detach().cpu().numpy() for k, v in outputs.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, len(a) * DUMP_MAX_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ---------------------------------------------------------------------------------------------- main
 def main():
     ap = argparse.ArgumentParser()
@@ -297,7 +322,12 @@ def main():
     ap.add_argument("--nineq", type=int, default=None)
     ap.add_argument("--neq", type=int, default=None)
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed region, also measure what the headline does not need: the round 1-4 protocol, 10-step "
+                         "chunks, the other BASELINE.json configurations, per-kernel times and the roofline, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (zhat, gradients) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: leave zhat on its rank (no all_gather)")
     ap.add_argument("--shared", action="store_true",
                     help="Q, G, A shared by the batch (SURVEY 8f-1): one pre-factorisation for the whole batch, "
@@ -307,12 +337,14 @@ def main():
                          "kernels serve the size (else 2); 0 = the float32 loop kernel alone; k = float32 kernels + k "
                          "finishing iterations on the residuals of the original data.  float64: default 0")
     ap.add_argument("--no-side-configs", action="store_true",
-                    help="default command only: do not time BASELINE.json's C3 and C4 behind the headline (extra.other_baseline_configs)")
+                    help="--full, default command only: do not time BASELINE.json's C3 and C4 behind the headline (extra.other_baseline_configs)")
     ap.add_argument("--step-kernels-only", action="store_true",
-                    help="profiling runs: skip the launches a step does not contain (the loop with early stopping off, the backward "
+                    help="--full profiling runs: skip the launches a step does not contain (the loop with early stopping off, the backward "
                          "with every gradient, the forward under no_grad), so that per-kernel averages and PMC sums are the step's")
     ap.add_argument("--table", default=None, choices=["prof-linear", "prof-gurobi"])
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -370,42 +402,47 @@ def main():
     gather = distributed and not args.no_gather
 
     def step():
+        """one step; returns what it hands its caller: zhat and the gradients it asks for (--dump-outputs)"""
         z = qpf(tQ, tp, tG, th, tA, tb)
         # zhat for the caller's autograd graph: the all_gather runs on RCCL's stream BESIDE the backward launches
         # (the backward needs nothing from the other ranks) and is waited for at the end of the step
         pending = qdist.gather_batch(z.detach(), global_B, async_op=True) if gather else None
         z.backward(ones)
+        outs = {"zhat": z, "dp": tp.grad}
         if pending is not None:
-            pending.wait()
+            outs["zhat_gathered"] = pending.wait()
+        if args.shared:
+            outs["dQ"], outs["dG"] = tQ.grad, tG.grad
         if args.shared and distributed:
-            qdist.reduce_shared_grad(tQ.grad, B, global_B)
-            qdist.reduce_shared_grad(tG.grad, B, global_B)
+            outs["dQ"] = qdist.reduce_shared_grad(tQ.grad, B, global_B)
+            outs["dG"] = qdist.reduce_shared_grad(tG.grad, B, global_B)
         tp.grad = None
         if args.shared:
             tQ.grad = None
             tG.grad = None
-        return z
+        return outs
 
     def barrier():
         if distributed:
             dist.barrier()
         torch.cuda.synchronize()
 
-    # the protocol of rounds 1-4, kept so that rounds stay comparable: W warm-up steps, then 20 timed steps, as the process'
-    # first GPU work (un-spun)
-    for _ in range(args.warmup):
-        step()
-    barrier()
-    u0 = time.perf_counter()
-    for _ in range(20):
-        step()
-    barrier()
-    first20 = time.perf_counter() - u0
-    if distributed:
-        tt = torch.tensor([first20], dtype=torch.float64, device=dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        first20 = float(tt.item())
-    wall["setup_and_first_20_steps"] = time.perf_counter() - t_start
+    if args.full:
+        # the protocol of rounds 1-4, kept so that rounds stay comparable: W warm-up steps, then 20 timed steps, as the process'
+        # first GPU work (un-spun)
+        for _ in range(args.warmup):
+            step()
+        barrier()
+        u0 = time.perf_counter()
+        for _ in range(20):
+            step()
+        barrier()
+        first20 = time.perf_counter() - u0
+        if distributed:
+            tt = torch.tensor([first20], dtype=torch.float64, device=dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            first20 = float(tt.item())
+    wall["setup_and_first_20_steps" if args.full else "setup"] = time.perf_counter() - t_start
     # untimed: the device's clocks and the allocator settle (a fresh box runs its first few hundred steps up to 7 % slower than
     # its later ones: 774 K against 831 K QPs/s in profiles/r05v_spin_up.txt; 1-2 % in a process on a box that has already
     # worked); the warm-up proper follows.  The timed region is exactly `steps` steps.
@@ -428,7 +465,7 @@ def main():
     wall["spin_up_and_warmup"] = time.perf_counter() - w0
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
     wall["timed_region"] = dt
@@ -438,35 +475,41 @@ def main():
         dt = float(tt.item())
     ms_per_step = dt / args.steps * 1e3
     value = global_B * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        w0 = time.perf_counter()
+        dump_outputs(args.dump_outputs, last)
+        wall["dump_outputs"] = time.perf_counter() - w0
+    del last
 
-    # median over chunks of 10 steps: the box-to-box and run-to-run spread the single total hides (every rank
-    # runs them: a step contains collectives at N > 1)
-    w0 = time.perf_counter()
-    chunk_ms = []
-    for _ in range(min(10, max(3, args.steps // 10))):
-        barrier()
-        c0 = time.perf_counter()
-        for _ in range(10):
-            step()
-        barrier()
-        chunk_ms.append((time.perf_counter() - c0) / 10 * 1e3)
-
-    # N > 1 on the default configuration: the line ALSO carries the north star's strong-scaling point (BASELINE.json
-    # configs[4]: C5, fixed GLOBAL batch 65 536, nz = nineq = 64, contiguous slices, zhat all_gathered), so that whichever
-    # command the driver runs at N = 1, 2, 4, 8 the record holds both readings of the metric.  Every rank takes part.
-    wall["median_chunks"] = time.perf_counter() - w0
-    w0 = time.perf_counter()
     extra = None
-    if distributed and args.config == "c2" and not args.shared and all(v is None for v in (args.batch, args.nz, args.nineq, args.neq)):
-        extra = {"c5_strong_scaling": c5_point(rank, world, dev, tQ.dtype, barrier)}
-    if (not distributed and args.config == "c2" and not args.shared and args.dtype == "f64" and args.refine is None
-            and not args.no_side_configs and all(v is None for v in (args.batch, args.nz, args.nineq, args.neq))):
-        # every BASELINE.json configuration that fits one GPU behind the headline, so that the driver's record holds them:
-        # C3, C4 and -- round 6 -- C5's 65 536 QPs on this one GPU (the point the 1/2/4/8 curve starts from)
-        extra = {"other_baseline_configs": {"c3": side_config(dev, 512, 100, 50, 10, 100, 10),
-                                            "c4": side_config(dev, 128, 500, 500, 0, 10, 2),
-                                            "c5_one_gpu": side_config(dev, 65536, 64, 64, 0, 5, 2, on_device=True)}}
-    wall["side_configs"] = time.perf_counter() - w0
+    if args.full:
+        # median over chunks of 10 steps: the box-to-box and run-to-run spread the single total hides (every rank
+        # runs them: a step contains collectives at N > 1)
+        w0 = time.perf_counter()
+        chunk_ms = []
+        for _ in range(min(10, max(3, args.steps // 10))):
+            barrier()
+            c0 = time.perf_counter()
+            for _ in range(10):
+                step()
+            barrier()
+            chunk_ms.append((time.perf_counter() - c0) / 10 * 1e3)
+
+        # N > 1 on the default configuration: the line ALSO carries the north star's strong-scaling point (BASELINE.json
+        # configs[4]: C5, fixed GLOBAL batch 65 536, nz = nineq = 64, contiguous slices, zhat all_gathered), so that a --full
+        # record at N = 1, 2, 4, 8 holds both readings of the metric.  Every rank takes part.
+        wall["median_chunks"] = time.perf_counter() - w0
+        w0 = time.perf_counter()
+        if distributed and args.config == "c2" and not args.shared and all(v is None for v in (args.batch, args.nz, args.nineq, args.neq)):
+            extra = {"c5_strong_scaling": c5_point(rank, world, dev, tQ.dtype, barrier)}
+        if (not distributed and args.config == "c2" and not args.shared and args.dtype == "f64" and args.refine is None
+                and not args.no_side_configs and all(v is None for v in (args.batch, args.nz, args.nineq, args.neq))):
+            # every BASELINE.json configuration that fits one GPU behind the headline, so that a --full record holds them:
+            # C3, C4 and -- round 6 -- C5's 65 536 QPs on this one GPU (the point the 1/2/4/8 curve starts from)
+            extra = {"other_baseline_configs": {"c3": side_config(dev, 512, 100, 50, 10, 100, 10),
+                                                "c4": side_config(dev, 128, 500, 500, 0, 10, 2),
+                                                "c5_one_gpu": side_config(dev, 65536, 64, 64, 0, 5, 2, on_device=True)}}
+        wall["side_configs"] = time.perf_counter() - w0
     w0 = time.perf_counter()
 
     # float32 data at a size the float64 tile kernels serve runs in float64 arithmetic (QPFunction(refine=None),
@@ -474,7 +517,7 @@ def main():
     from qpth_amd.qp import f64_arithmetic_serves
     wide = args.dtype == "f32" and args.refine is None and f64_arithmetic_serves(n, m, q, _lib.hip())
     arith = "f64" if wide else args.dtype
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- per-kernel timing with HIP events on the launch stream (torch's current stream) ----
         dQ, dG, dA = tQ.detach(), tG.detach(), tA.detach() if q else tA
         kp, kh, kb, ones_k = tp.detach(), th, tb, ones
@@ -603,6 +646,7 @@ def main():
                             "reference_pytorch_cpu": reference_cpu_record(args.dtype)}
 
         wall["cpu_baseline"] = time.perf_counter() - w0
+    if rank == 0:
         wall["total"] = time.perf_counter() - t_start
         names = {"c2": "C2", "c3": "C3", "c4": "C4", "c5": "C5", "custom": "custom"}
         out = {
@@ -619,22 +663,26 @@ def main():
                        "global_batch": global_B, "parallelism": "batch-sharded x%d" % world,
                        "tensor_dtype": args.dtype,
                        "arithmetic": ("float64 kernels on float32 tensors (QPX_F32_WIDE: widened on load, narrowed on store, "
-                                      "float64 factors)" if wide else arith),
-                       "ipm_iterations_mean": iters_mean, "ipm_iterations_max": int(iters.max()),
-                       "ipm_iterations_histogram": np.bincount(iters, minlength=21).tolist()},
-            "roofline": roofline,
-            "cpu_baseline": cpu_baseline,
-            "ms_per_step_median_of_10_step_chunks": float(np.median(chunk_ms)),
-            "first_20_steps_qps": global_B * 20 / first20,
-            "first_20_steps_what": "the protocol of rounds 1-4 in this same process: %d warm-up steps, then 20 timed steps, as the "
-                                   "process' first GPU work, before the untimed spin-up" % args.warmup,
-            "wall_s": {k: round(v, 3) for k, v in wall.items()},
-            "fwd_only": None if t_fwd is None else {"qps": B / t_fwd, "ms": t_fwd * 1e3, "what": "QPFunction forward under no_grad (BASELINE.json configs[1])"},
-            "kernel_ms": {"pre_factor": t_pre * 1e3, "ipm": t_ipm * 1e3, "backward": t_bwd * 1e3,
-                          "backward_all_gradients": None if t_bwd_all is None else t_bwd_all * 1e3,
-                          "ipm_all_20_iterations": None if t_ipm_fixed is None else t_ipm_fixed * 1e3},
-            "job_hbm_roofline_frac": value / world * (fwd_r + fwd_w + bwd_r + bwd_w) / HBM_PEAK,
+                                      "float64 factors)" if wide else arith)},
         }
+        if args.full:
+            out["config"].update({"ipm_iterations_mean": iters_mean, "ipm_iterations_max": int(iters.max()),
+                                  "ipm_iterations_histogram": np.bincount(iters, minlength=21).tolist()})
+            out.update({
+                "roofline": roofline,
+                "cpu_baseline": cpu_baseline,
+                "ms_per_step_median_of_10_step_chunks": float(np.median(chunk_ms)),
+                "first_20_steps_qps": global_B * 20 / first20,
+                "first_20_steps_what": "the protocol of rounds 1-4 in this same process: %d warm-up steps, then 20 timed steps, as "
+                                       "the process' first GPU work, before the untimed spin-up" % args.warmup})
+        out["wall_s"] = {k: round(v, 3) for k, v in wall.items()}
+        if args.full:
+            out.update({
+                "fwd_only": None if t_fwd is None else {"qps": B / t_fwd, "ms": t_fwd * 1e3, "what": "QPFunction forward under no_grad (BASELINE.json configs[1])"},
+                "kernel_ms": {"pre_factor": t_pre * 1e3, "ipm": t_ipm * 1e3, "backward": t_bwd * 1e3,
+                              "backward_all_gradients": None if t_bwd_all is None else t_bwd_all * 1e3,
+                              "ipm_all_20_iterations": None if t_ipm_fixed is None else t_ipm_fixed * 1e3},
+                "job_hbm_roofline_frac": value / world * (fwd_r + fwd_w + bwd_r + bwd_w) / HBM_PEAK})
         if extra is not None:
             out["extra"] = extra
         print(json.dumps(out))

@@ -19,20 +19,20 @@ timeout 900 python -m pytest tests -m gpu -q -x --timeout 600 > $OUT/pytest_gpu.
 tail -15 $OUT/pytest_gpu.log >> $OUT/summary.txt
 fi
 echo "== bench" | tee -a $OUT/summary.txt
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?" | tee -a $OUT/summary.txt
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?" | tee -a $OUT/summary.txt
 cat $OUT/bench.json >> $OUT/summary.txt; tail -5 $OUT/bench.err >> $OUT/summary.txt
-timeout 300 python bench.py --dtype f32 --no-cpu-baseline > $OUT/bench_f32.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --dtype f32 --no-cpu-baseline > $OUT/bench_f32.json 2>> $OUT/bench.err
 cat $OUT/bench_f32.json >> $OUT/summary.txt
 echo "== rocprofv3 kernel stats" | tee -a $OUT/summary.txt
-CMD="python $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+CMD="python $REPO/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_stats -o stats -- $CMD > $REPO/$OUT/prof_stats.log 2>&1); echo "rocprof stats exit $?" | tee -a $OUT/summary.txt
-{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline"; echo "# bench line of that run:"; grep '^{' $OUT/prof_stats.log | sed 's/^/# /';
+{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"; echo "# bench line of that run:"; grep '^{' $OUT/prof_stats.log | sed 's/^/# /';
   find /tmp/prof_stats -name "*.db" | while read f; do python scripts/rocprof_summary.py "$f"; done; } > $PROF/${TAG}_kernel_stats.txt 2>&1
 cat $PROF/${TAG}_kernel_stats.txt >> $OUT/summary.txt
 echo "== rocprofv3 pmc" | tee -a $OUT/summary.txt
 for C in FETCH_SIZE WRITE_SIZE; do
-  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc $C -d /tmp/prof_pmc_$C -o pmc -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $REPO/$OUT/prof_pmc_$C.log 2>&1); echo "pmc $C exit $?" | tee -a $OUT/summary.txt
-  { echo "# rocprofv3 --kernel-trace --pmc $C -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+  (cd $TMPDIR && timeout 600 rocprofv3 --kernel-trace --pmc $C -d $TMPDIR/prof_pmc_$C -o pmc -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $REPO/$OUT/prof_pmc_$C.log 2>&1); echo "pmc $C exit $?" | tee -a $OUT/summary.txt
+  { echo "# rocprofv3 --kernel-trace --pmc $C -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"
     find /tmp/prof_pmc_$C -name "*.db" | while read f; do python scripts/rocprof_summary.py "$f"; done; } > $PROF/${TAG}_pmc_$C.txt 2>&1
   cat $PROF/${TAG}_pmc_$C.txt >> $OUT/summary.txt
 done

@@ -16,7 +16,7 @@ echo "== smoke" > $S
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke exit $? ($(el))" >> $S
 tail -2 $OUT/smoke.log >> $S
 echo "== bench (default: C2 f64; extra: C3, C4)" >> $S
-timeout 400 python bench.py > $PROF/${TAG}_bench_f64.json 2> $OUT/bench.err; echo "bench exit $? ($(el))" >> $S
+timeout 400 python bench.py --full > $PROF/${TAG}_bench_f64.json 2> $OUT/bench.err; echo "bench exit $? ($(el))" >> $S
 cat $PROF/${TAG}_bench_f64.json >> $S
 if [ -z "$SKIP_TESTS" ]; then
 echo "== pytest -m gpu" >> $S
@@ -26,40 +26,40 @@ grep -v amdgpu.ids $OUT/pytest_gpu.log | tail -18 >> $S
 grep -v amdgpu.ids $OUT/pytest_gpu.log > $PROF/${TAG}_pytest_gpu.txt
 fi
 echo "== rocprofv3 kernel stats + PMC (default bench)" >> $S
-CMD="python $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-side-configs"
+CMD="python $REPO/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-side-configs"
 (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_stats -o stats -- $CMD > $REPO/$OUT/prof_stats.log 2>&1); echo "rocprof stats exit $? ($(el))" >> $S
-{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-side-configs"; echo "# bench line of that run:"; grep '^{' $OUT/prof_stats.log | sed 's/^/# /';
+{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-side-configs"; echo "# bench line of that run:"; grep '^{' $OUT/prof_stats.log | sed 's/^/# /';
   find /tmp/prof_stats -name "*.db" | while read f; do python scripts/rocprof_summary.py "$f"; done; } > $PROF/${TAG}_kernel_stats.txt 2>&1
 head -24 $PROF/${TAG}_kernel_stats.txt | cut -c1-300 >> $S
 for C in FETCH_SIZE WRITE_SIZE; do
-  (cd /tmp && timeout 400 rocprofv3 --kernel-trace --pmc $C -d /tmp/prof_pmc_$C -o pmc -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-side-configs > $REPO/$OUT/prof_pmc_$C.log 2>&1); echo "pmc $C exit $? ($(el))" >> $S
-  { echo "# rocprofv3 --kernel-trace --pmc $C -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-side-configs"
+  (cd $TMPDIR && timeout 400 rocprofv3 --kernel-trace --pmc $C -d $TMPDIR/prof_pmc_$C -o pmc -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-side-configs > $REPO/$OUT/prof_pmc_$C.log 2>&1); echo "pmc $C exit $? ($(el))" >> $S
+  { echo "# rocprofv3 --kernel-trace --pmc $C -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-side-configs"
     find /tmp/prof_pmc_$C -name "*.db" | while read f; do python scripts/rocprof_summary.py "$f"; done; } > $PROF/${TAG}_pmc_$C.txt 2>&1
 done
 python scripts/make_traffic_json.py $PROF/${TAG}_pmc_FETCH_SIZE.txt $PROF/${TAG}_pmc_WRITE_SIZE.txt > $PROF/ipm_traffic.json 2>> $S
 cat $PROF/ipm_traffic.json >> $S
 echo "== other configurations" >> $S
-timeout 200 python bench.py --dtype f32 --no-cpu-baseline > $PROF/${TAG}_bench_f32.json 2>> $OUT/bench.err
-timeout 200 python bench.py --dtype f32 --refine 0 --no-cpu-baseline > $PROF/${TAG}_bench_f32_refine0.json 2>> $OUT/bench.err
-timeout 200 python bench.py --dtype f32 --refine 2 --no-cpu-baseline > $PROF/${TAG}_bench_f32_refine2.json 2>> $OUT/bench.err
-timeout 200 python bench.py --shared --no-cpu-baseline > $PROF/${TAG}_bench_shared.json 2>> $OUT/bench.err
-timeout 200 python bench.py --config c3 --no-cpu-baseline > $PROF/${TAG}_bench_c3.json 2>> $OUT/bench.err
-timeout 300 python bench.py --config c4 --steps 20 --warmup 3 > $PROF/${TAG}_bench_c4.json 2>> $OUT/bench.err
-timeout 300 python bench.py --config c4 --dtype f32 --steps 20 --warmup 3 --no-cpu-baseline > $PROF/${TAG}_bench_c4_f32.json 2>> $OUT/bench.err
-timeout 300 python bench.py --config c4 --dtype f32 --refine 2 --steps 10 --warmup 2 --no-cpu-baseline > $PROF/${TAG}_bench_c4_f32_refine2.json 2>> $OUT/bench.err
-timeout 300 python bench.py --config custom --batch 128 --nz 500 --nineq 400 --neq 100 --steps 20 --warmup 3 --no-cpu-baseline > $PROF/${TAG}_bench_c4_neq100.json 2>> $OUT/bench.err
-timeout 300 python bench.py --config custom --batch 512 --nz 150 --nineq 150 --neq 0 --steps 20 --warmup 3 --no-cpu-baseline > $PROF/${TAG}_bench_b512_n150_m150.json 2>> $OUT/bench.err
-timeout 300 python bench.py --config c5 --steps 10 --warmup 2 --no-cpu-baseline > $PROF/${TAG}_bench_c5_one_gpu.json 2>> $OUT/bench.err
+timeout 200 python bench.py --full --dtype f32 --no-cpu-baseline > $PROF/${TAG}_bench_f32.json 2>> $OUT/bench.err
+timeout 200 python bench.py --full --dtype f32 --refine 0 --no-cpu-baseline > $PROF/${TAG}_bench_f32_refine0.json 2>> $OUT/bench.err
+timeout 200 python bench.py --full --dtype f32 --refine 2 --no-cpu-baseline > $PROF/${TAG}_bench_f32_refine2.json 2>> $OUT/bench.err
+timeout 200 python bench.py --full --shared --no-cpu-baseline > $PROF/${TAG}_bench_shared.json 2>> $OUT/bench.err
+timeout 200 python bench.py --full --config c3 --no-cpu-baseline > $PROF/${TAG}_bench_c3.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --config c4 --steps 20 --warmup 3 > $PROF/${TAG}_bench_c4.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --config c4 --dtype f32 --steps 20 --warmup 3 --no-cpu-baseline > $PROF/${TAG}_bench_c4_f32.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --config c4 --dtype f32 --refine 2 --steps 10 --warmup 2 --no-cpu-baseline > $PROF/${TAG}_bench_c4_f32_refine2.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --config custom --batch 128 --nz 500 --nineq 400 --neq 100 --steps 20 --warmup 3 --no-cpu-baseline > $PROF/${TAG}_bench_c4_neq100.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --config custom --batch 512 --nz 150 --nineq 150 --neq 0 --steps 20 --warmup 3 --no-cpu-baseline > $PROF/${TAG}_bench_b512_n150_m150.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --config c5 --steps 10 --warmup 2 --no-cpu-baseline > $PROF/${TAG}_bench_c5_one_gpu.json 2>> $OUT/bench.err
 for f in f32 f32_refine0 f32_refine2 shared c3 c4 c4_f32 c4_f32_refine2 c4_neq100 b512_n150_m150 c5_one_gpu; do echo "-- $f" >> $S; cut -c1-420 $PROF/${TAG}_bench_$f.json >> $S; grep -o '"kernel_ms": {[^}]*}' $PROF/${TAG}_bench_$f.json >> $S; done
 echo "($(el))" >> $S
 echo "== C4: rocprofv3 kernel stats + PMC" >> $S
-CMD4="python $REPO/bench.py --config c4 --steps 3 --warmup 1 --no-cpu-baseline"
+CMD4="python $REPO/bench.py --full --config c4 --steps 3 --warmup 1 --no-cpu-baseline"
 (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_stats4 -o stats -- $CMD4 > $REPO/$OUT/prof_stats4.log 2>&1); echo "rocprof c4 stats exit $? ($(el))" >> $S
-{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --config c4 --steps 3 --warmup 1 --no-cpu-baseline"; grep '^{' $OUT/prof_stats4.log | cut -c1-600 | sed 's/^/# /';
+{ echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --config c4 --steps 3 --warmup 1 --no-cpu-baseline"; grep '^{' $OUT/prof_stats4.log | cut -c1-600 | sed 's/^/# /';
   find /tmp/prof_stats4 -name "*.db" | while read f; do python scripts/rocprof_summary.py "$f"; python scripts/rocprof_timeline.py "$f" --last 800 > $PROF/${TAG}_c4_timeline.txt 2>&1; done; } > $PROF/${TAG}_c4_kernel_stats.txt 2>&1
 for C in FETCH_SIZE WRITE_SIZE; do
   (cd /tmp && timeout 400 rocprofv3 --kernel-trace --pmc $C -d /tmp/prof_pmc4_$C -o pmc -- $CMD4 > $REPO/$OUT/prof_pmc4_$C.log 2>&1); echo "pmc c4 $C exit $? ($(el))" >> $S
-  { echo "# rocprofv3 --kernel-trace --pmc $C -- python bench.py --config c4 --steps 3 --warmup 1 --no-cpu-baseline"
+  { echo "# rocprofv3 --kernel-trace --pmc $C -- python bench.py --full --config c4 --steps 3 --warmup 1 --no-cpu-baseline"
     find /tmp/prof_pmc4_$C -name "*.db" | while read f; do python scripts/rocprof_summary.py "$f"; done; } > $PROF/${TAG}_c4_pmc_$C.txt 2>&1
 done
 head -22 $PROF/${TAG}_c4_kernel_stats.txt | cut -c1-300 >> $S

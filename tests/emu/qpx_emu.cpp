@@ -50,16 +50,73 @@ static int emu_threads()
 }
 
 #ifdef QPX_EMU_PTHREADS
-template <class Body> struct ThreadCtx {
-    const Body* body;
-    Block blk;
+// The nt threads of a workgroup size live as long as the process: under ThreadSanitizer, creating and joining 256
+// threads for every workgroup cost ~85 ms, most of a sanitizer run.  A launch is bracketed by the pool's two barriers
+// (nt workers + the launching thread), which order it after everything before and before everything after, as
+// pthread_create / pthread_join did; inside the launch only the kernel's own barriers order the threads.
+struct WorkerPool;
+struct WorkerArg {
+    WorkerPool* pool;
+    int t;
 };
 
-template <class Body> static void* thread_main(void* p)
+struct WorkerPool {
+    int nt = 0;
+    pthread_barrier_t start, done;
+    void (*run)(const void* body, const Block& blk) = nullptr;
+    const void* body = nullptr;
+    EmuShared* sh = nullptr;
+    bool quit = false;
+    std::vector<WorkerArg> args;
+    std::vector<pthread_t> th;
+};
+
+static void* worker_main(void* p)
 {
-    auto* c = static_cast<ThreadCtx<Body>*>(p);
-    (*c->body)(c->blk);
-    return nullptr;
+    const WorkerArg* a = static_cast<const WorkerArg*>(p);
+    WorkerPool* P = a->pool;
+    for (;;) {
+        pthread_barrier_wait(&P->start);
+        if (P->quit) return nullptr;
+        P->run(P->body, Block{a->t, P->nt, P->sh});
+        pthread_barrier_wait(&P->done);
+    }
+}
+
+static WorkerPool* pool_for(int nt)
+{
+    static struct Pools {
+        std::vector<WorkerPool*> all;
+        ~Pools()
+        {
+            for (WorkerPool* P : all) {
+                P->quit = true;
+                pthread_barrier_wait(&P->start);
+                for (pthread_t t : P->th) pthread_join(t, nullptr);
+                pthread_barrier_destroy(&P->start);
+                pthread_barrier_destroy(&P->done);
+                delete P;
+            }
+        }
+    } pools;
+    for (WorkerPool* P : pools.all)
+        if (P->nt == nt) return P;
+    auto* P = new WorkerPool;
+    P->nt = nt;
+    pthread_barrier_init(&P->start, nullptr, nt + 1);
+    pthread_barrier_init(&P->done, nullptr, nt + 1);
+    P->args.resize(nt);
+    P->th.resize(nt);
+    pthread_attr_t attr;
+    pthread_attr_init(&attr);
+    pthread_attr_setstacksize(&attr, 1 << 20);
+    for (int t = 0; t < nt; ++t) {
+        P->args[t] = WorkerArg{P, t};
+        pthread_create(&P->th[t], &attr, worker_main, &P->args[t]);
+    }
+    pthread_attr_destroy(&attr);
+    pools.all.push_back(P);
+    return P;
 }
 
 // run `body(block)` for one workgroup
@@ -77,18 +134,12 @@ template <class Body> static void run_block(int nt, const Body& body)
     sh.xchg2 = xchg2.data();
     std::vector<double> xv((size_t)nt * 16, 0.0);
     sh.xv = xv.data();
-    std::vector<ThreadCtx<Body>> ctx(nt);
-    std::vector<pthread_t> th(nt);
-    pthread_attr_t attr;
-    pthread_attr_init(&attr);
-    pthread_attr_setstacksize(&attr, 1 << 20);
-    for (int t = 0; t < nt; ++t) {
-        ctx[t].body = &body;
-        ctx[t].blk = Block{t, nt, &sh};
-        pthread_create(&th[t], &attr, thread_main<Body>, &ctx[t]);
-    }
-    for (int t = 0; t < nt; ++t) pthread_join(th[t], nullptr);
-    pthread_attr_destroy(&attr);
+    WorkerPool* P = pool_for(nt);
+    P->run = [](const void* b, const Block& blk) { (*static_cast<const Body*>(b))(blk); };
+    P->body = &body;
+    P->sh = &sh;
+    pthread_barrier_wait(&P->start);
+    pthread_barrier_wait(&P->done);
     for (int w = 0; w < nw; ++w) pthread_barrier_destroy(&wb[w]);
     pthread_barrier_destroy(&sh.block_bar);
 }

@@ -452,7 +452,7 @@ def test_kernel_bodies_are_race_free_under_thread_sanitizer():
     import os
     import subprocess
     here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-    subprocess.check_call(["make", "-C", here, "-s", "tsan"], timeout=900)     # ~95 s to build, ~35 s to run
+    subprocess.check_call(["make", "-C", here, "-s", "tsan"], timeout=900)     # ~2 min to build (build() does), ~70 s to run
 
 
 @pytest.mark.parametrize("name", ["edge_b3_n1_m1_q0", "edge_b2_n6_m4_q5", "edge_dup_b2_n8_m10_q0"])

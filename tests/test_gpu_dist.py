@@ -116,7 +116,7 @@ def _bench_line(cmd, env, timeout):
 
 
 def test_bench_distributed_branch_world_size_one(tmp_path):
-    """bench.py --gpus 1 with QPX_FORCE_DIST=1: the branch the driver's N > 1 runs take (RCCL process group, zhat
+    """bench.py --gpus 1 --full with QPX_FORCE_DIST=1: the branch the driver's N > 1 runs take (RCCL process group, zhat
     all_gathered beside the backward inside the timed region, MAX over ranks, the C5 strong-scaling point under `extra`)
     on the one GPU of this box.  The record is kept under gpurun_out/ when that directory exists."""
     import json
@@ -124,7 +124,7 @@ def test_bench_distributed_branch_world_size_one(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", QPX_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
-    d = _bench_line([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--no-cpu-baseline"],
+    d = _bench_line([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--full", "--steps", "20", "--warmup", "3", "--no-cpu-baseline"],
                     env, 900)
     assert d["n_gpus"] == 1 and d["scaling"] == "weak" and d["config"]["global_batch"] == 512 and d["value"] > 0
     assert "all_gathered over RCCL" in d["config"]["workload"]
@@ -160,8 +160,8 @@ def test_bench_strong_scaling_contract_under_torchrun(tmp_path):
 
 
 def test_default_bench_line_carries_both_readings_of_the_metric_at_n_gpus(tmp_path):
-    """The DEFAULT bench.py --gpus N (what the driver runs for the scaling curve): weak C2 as `value` and, under
-    `extra.c5_strong_scaling`, the north star's fixed global batch of 65 536 over the same N ranks (round 4).  Needs >= 2
+    """The DEFAULT bench.py --gpus N --full: weak C2 as `value` and, under `extra.c5_strong_scaling`, the north
+    star's fixed global batch of 65 536 over the same N ranks (round 4).  Needs >= 2
     visible GPUs."""
     import json
     import subprocess
@@ -172,8 +172,8 @@ def test_default_bench_line_carries_both_readings_of_the_metric_at_n_gpus(tmp_pa
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "20", "--warmup", "3",
-           "--no-cpu-baseline"]
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(world), "--full", "--steps", "20",
+           "--warmup", "3", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, check=True, env=env).stdout
     lines = [ln for ln in out.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1

@@ -1020,14 +1020,14 @@ def test_every_loop_kernel_form_against_the_reference(dev, variant, name):
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields(dev):
-    """bench.py is what the driver times: one JSON line on stdout, the metric of BASELINE.json, the roofline
-    object of the dominant kernel.  (Short run, no CPU baseline.)"""
+    """bench.py --full: one JSON line on stdout, the metric of BASELINE.json, the roofline object of the dominant
+    kernel.  (Short run, no CPU baseline.)"""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                           "--no-cpu-baseline"], capture_output=True, text=True, timeout=280, check=True).stdout
     lines = [ln for ln in out.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -1042,10 +1042,41 @@ def test_bench_prints_one_json_line_with_the_contract_fields(dev):
     for key in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert key in rf, key
     assert rf["bound"] in ("hbm", "mfma") and 0 < rf["frac"] < 1
-    # the default command also carries BASELINE.json's C3 and C4, timed the same way behind the headline (round 5)
+    # the default command with --full also carries BASELINE.json's C3 and C4, timed the same way behind the headline
     side = d["extra"]["other_baseline_configs"]
     for key, B in (("c3", 512), ("c4", 128)):
         assert side[key]["value"] > 0 and abs(side[key]["value"] - B / (side[key]["ms_per_step"] * 1e-3)) < 1e-6 * side[key]["value"]
+
+
+def test_plain_bench_times_its_steps_and_dumps_what_they_returned(dev, tmp_path):
+    """bench.py without --full: the headline fields only, `steps` timed steps, and --dump-outputs writes the last step's
+    zhat and dp -- the answer QPFunction gives on the same seeded C2 batch."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=280, check=True).stdout
+    lines = [ln for ln in out.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("QPs/sec (fwd+bwd) at batch=512 nz=100 nineq=100")
+    assert d["unit"] == "QPs/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["steps"] == 7
+    assert d["value"] > 0 and abs(d["value"] - 512 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for key in ("roofline", "cpu_baseline", "extra", "kernel_ms", "first_20_steps_qps"):
+        assert key not in d, key
+    assert sorted(os.listdir(tmp_path)) == ["dp.npy", "zhat.npy"]
+    z_dump, dp_dump = np.load(tmp_path / "zhat.npy"), np.load(tmp_path / "dp.npy")
+    assert z_dump.dtype == np.float64 and z_dump.shape == (512, 100) and dp_dump.shape == (512, 100)
+    from qpth_amd.qp import QPFunction
+    tq = to_dev(problems.prof_qp(512, 100, 100, 0, seed=0), dev, grad=False)
+    tq[1].requires_grad_(True)                              # p alone, as in bench.py's step
+    zt = QPFunction(verbose=-1)(*tq)
+    zt.backward(torch.ones_like(zt))
+    z, dp = zt.detach().cpu().numpy(), tq[1].grad.cpu().numpy()
+    assert rel_err(z_dump, z).max() < 1e-9
+    assert np.abs(dp_dump - dp).max() <= 1e-9 * max(1.0, np.abs(dp).max())
 
 
 def test_max_iter_and_eps_are_honoured(dev):

@@ -155,3 +155,27 @@ def test_unpack_kkt_and_kkt_resid_reg_mirror_the_reference():
     assert torch.allclose(res2[2], -eps * bump, atol=1e-10)
     rx3, rs3, rz3, _ = pb.kkt_resid_reg(t(Q), t(D), t(G), None, eps, dx, ds, dz, None, t(rx), t(rs), t(rz), None)
     assert _ is None and rx3.shape == (B, nz)
+
+
+def test_bench_dump_outputs_writes_each_tensor_and_one_seeded_sample_of_rows_over_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every tensor a step returned as <name>.npy in its own dtype; over the size cap, every
+    tensor keeps the same share of rows, the same rows from run to run (so two builds compare output for output)."""
+    import numpy as np
+    import bench
+    z = torch.arange(1000, dtype=torch.float64).reshape(100, 10)
+    outputs = {"zhat": z, "dp": (-z).float(), "dQ": None}
+    bench.dump_outputs(str(tmp_path / "whole"), outputs)
+    assert sorted(p.name for p in (tmp_path / "whole").iterdir()) == ["dp.npy", "zhat.npy"]
+    whole = np.load(tmp_path / "whole" / "zhat.npy")
+    assert whole.dtype == np.float64 and np.array_equal(whole, z.numpy())
+    assert np.load(tmp_path / "whole" / "dp.npy").dtype == np.float32
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)                 # 8000 + 4000 bytes in all
+    bench.dump_outputs(str(tmp_path / "a"), outputs)
+    bench.dump_outputs(str(tmp_path / "b"), outputs)
+    za, da = np.load(tmp_path / "a" / "zhat.npy"), np.load(tmp_path / "a" / "dp.npy")
+    assert za.nbytes + da.nbytes <= 4000 and len(za) == len(da) > 0
+    rows = za[:, 0] / 10
+    assert np.array_equal(rows, -da[:, 0] / 10) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(za, z.numpy()[rows.astype(int)])
+    assert np.array_equal(za, np.load(tmp_path / "b" / "zhat.npy"))
