@@ -13,6 +13,7 @@
  *   qpx_factor_solve_kkt .. qpth/solvers/pdipm/batch.py:435-470 + 349-372
  *                                                                  factor_kkt(S_LU,R,d); solve_kkt(...)
  *   qpx_backward .......... qpth/qp.py:127-182                     QPFunctionFn.backward (per-QP grads)
+ *   qpx_jvp ............... (no reference counterpart)            QPFunctionFn.jvp: forward mode, the adjoint of qpx_backward
  *
  * Conventions
  *   - dtype: QPX_F32 or QPX_F64: every `void*` array below has that element type; or QPX_F32_WIDE (see the enum).
@@ -197,6 +198,24 @@ int qpx_backward(int dtype, int B, int n, int m, int q, void* factors, int64_t s
                  void* dx, void* dz, void* dy,
                  int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
                  int32_t* status, qpx_stream_t stream);
+
+/* Additive after v8 (QPX_ABI_VERSION stays 8): FORWARD MODE of QPFunction -- the tangent of the solution at the given
+ * (zhat, lam, slack, nu) along tangents tQ (B,n,n), tp (B,n), tG (B,m,n), th (B,m), tA (B,q,n), tb (B,q) of the six
+ * parameters (each with its batch stride, 0 = shared; NULL = zero).  One KKT solve with the backward's matrix,
+ * d = clamp(lam, 1e-8) / clamp(slack, 1e-8) (qp.py:148), and the solver's convention K sol = -r (batch.py:349-372) with
+ *   rx = 1/2 (tQ + tQ^T) zhat + tp + tG^T lam + tA^T nu,   rs = 0,   rz = tG zhat - th,   ry = tA zhat - tb;
+ * dzhat (B,n) = dx (required); dlam (B,m) = dz, dnu (B,q) = dy, dslack (B,m) = ds = -dlam / d: optional (NULL = skip).
+ * Exactly the adjoint of qpx_backward: <dl_dz, dzhat> = <dQ, tQ> + <dp, tp> + <dG, tG> + <dh, th> + <dA, tA> + <db, tb>
+ * per QP.  dtype QPX_F32, QPX_F64 or QPX_F32_WIDE (the tangents and outputs float32 then); refine, Q, G, A and the checks
+ * as for qpx_backward (refine > 0 where qpx_refine_supported says so, else QPX_ERR_UNSUPPORTED); the large-QP family
+ * refuses sfac = 0 with B > 1.  A breakdown of the factorisation ORs QPX_ST_KKT_BREAKDOWN into status. */
+int qpx_jvp(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac,
+            const void* zhat, const void* lam, const void* slack, const void* nu,
+            const void* tQ, int64_t stQ, const void* tp, int64_t stp, const void* tG, int64_t stG,
+            const void* th, int64_t sth, const void* tA, int64_t stA, const void* tb, int64_t stb,
+            void* dzhat, void* dlam, void* dnu, void* dslack,
+            int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
+            int32_t* status, qpx_stream_t stream);
 
 /* v6: the FINISHING STAGE as one kernel -- `steps` iterations of the reference's PDIPM loop in the original variables
  * (qpth/solvers/pdipm/batch.py:92-198: affine + centring-corrector Newton steps, step lengths batch.py:189-198) started

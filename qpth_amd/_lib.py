@@ -46,6 +46,8 @@ _SIGNATURES = {
                                   _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "qpx_backward": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                           _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "qpx_jvp": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                     _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "qpx_polish_supported": (_i, [_i, _i, _i, _i]),
     "qpx_polish": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                         _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -176,6 +178,18 @@ class QpxLib:
             _ptr(nu), _ptr(dl_dz), _ptr(dQ), _ptr(dp), _ptr(dG), _ptr(dh), _ptr(dA), _ptr(db),
             _ptr(dx), _ptr(dz), _ptr(dy), int(refine), Qp.ptr, Qp.stride, Gp.ptr, Gp.stride, Ap.ptr, Ap.stride,
             _ptr(status), _stream(factors)))
+
+    # -- forward mode (QPFunctionFn.jvp): the tangent of the solution, one KKT solve with the backward's matrix
+    def jvp(self, B, n, m, q, factors, sfac, zhat, lam, slack, nu, tQ, tp, tG, th, tA, tb, dzhat, status,
+            dlam=None, dnu=None, dslack=None, refine=0, Q=None, G=None, A=None, wide=False):
+        """tQ .. tb: any may be None (zero); un-batched, batch-1 and expanded tangents go in with batch stride 0 (Param)"""
+        t = [Param(tQ, 3), Param(tp, 2), Param(tG, 3), Param(th, 2), Param(tA, 3), Param(tb, 2)]
+        Qp, Gp, Ap = Param(Q, 3), Param(G, 3), Param(A, 3)
+        self.check(self.dll.qpx_jvp(
+            _code(factors, wide), B, n, m, q, _ptr(factors), int(sfac), _ptr(zhat), _ptr(lam), _ptr(slack), _ptr(nu),
+            t[0].ptr, t[0].stride, t[1].ptr, t[1].stride, t[2].ptr, t[2].stride, t[3].ptr, t[3].stride,
+            t[4].ptr, t[4].stride, t[5].ptr, t[5].stride, _ptr(dzhat), _ptr(dlam), _ptr(dnu), _ptr(dslack),
+            int(refine), Qp.ptr, Qp.stride, Gp.ptr, Gp.stride, Ap.ptr, Ap.stride, _ptr(status), _stream(factors)))
 
     # -- batch.py:92-198 in the original variables, as a finishing stage (KKTSolvers.IR_UNOPT, float32 refine=k)
     def polish(self, B, n, m, q, Q, p, G, h, A, b, factors, sfac, steps, refine, zhat, nu, lam, slack, best_resid, status):

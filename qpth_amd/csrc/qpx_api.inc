@@ -542,6 +542,30 @@ int big_kkt_core(const BigCtx<T>& c, bool backward, bool factor)
     return QPX_OK;
 }
 
+// forward mode (qpx_jvp): the tangents' products on top of what stage 0 of big_kkt_body wrote (vU = tp, vRH = th, vBQ = -tb;
+// zhat, lam, nu at bvZ, bvS, bvY), by mat-vecs on the caller's row-major tangents:
+//   vU += 1/2 tQ zhat + 1/2 tQ^T zhat + tG^T lam + tA^T nu,   vRH -= tG zhat,   vBQ += tA zhat
+template <class T>
+int big_jvp_products(const BigCtx<T>& c, const KktArgs<T>& a)
+{
+    const BigLayout& L = c.L;
+    auto mv = [&](const T* M, long long sM, int rows, int trans, int x, int y, T alpha) {
+        BigGemvArgs<T> g{};
+        g.B = c.B; g.rows = rows; g.cols = c.n; g.trans = trans;
+        g.M = M; g.sM = (size_t)sM; g.ld = c.n; g.dense = 1; g.m32 = a.io32;
+        g.x = c.fac + L.v(x); g.sx = c.fs;
+        g.y0 = c.fac + L.v(y); g.sy0 = c.fs;
+        g.y = c.fac + L.v(y); g.sy = c.fs;
+        g.alpha = alpha; g.beta = T(1);
+        return launch_big_gemv<T>(g, c.stream);
+    };
+    int e;
+    if (a.tQ && ((e = mv(a.tQ, a.stQ, c.n, 0, bvZ, bvU, T(0.5))) || (e = mv(a.tQ, a.stQ, c.n, 1, bvZ, bvU, T(0.5))))) return e;
+    if (a.tG && ((e = mv(a.tG, a.stG, c.m, 1, bvS, bvU, T(1))) || (e = mv(a.tG, a.stG, c.m, 0, bvZ, bvRH, T(-1))))) return e;
+    if (c.q > 0 && a.tA && ((e = mv(a.tA, a.stA, c.q, 1, bvY, bvU, T(1))) || (e = mv(a.tA, a.stA, c.q, 0, bvZ, bvBQ, T(1))))) return e;
+    return QPX_OK;
+}
+
 template <class T, bool kBw>
 int big_kkt(const KktArgs<T>& a, void* stream)
 {
@@ -552,8 +576,14 @@ int big_kkt(const KktArgs<T>& a, void* stream)
     k.B = a.B; k.n = a.n; k.m = a.m; k.q = q; k.backward = kBw ? 1 : 0; k.fac = a.fac; k.fac_stride = a.fac_stride; k.io32 = a.io32;
     k.d = a.d; k.rx = a.rx; k.rs = a.rs; k.rz = a.rz; k.ry = a.ry; k.zhat = a.zhat; k.lam = a.lam; k.slack = a.slack; k.nu = a.nu; k.dl_dz = a.dl_dz;
     k.dx = a.dx; k.ds = a.ds; k.dz = a.dz; k.dy = a.dy; k.dQ = a.dQ; k.dp = a.dp; k.dG = a.dG; k.dh = a.dh; k.dA = a.dA; k.db = a.db; k.status = a.status;
+    if constexpr (!kBw) {
+        k.jvp = a.jvp; k.tp = a.tp; k.th = a.th; k.tb = a.tb; k.stp = a.stp; k.sth = a.sth; k.stb = a.stb;
+    }
     k.stage = 0;
     if ((e = launch_big_kkt<T>(k, 1, stream))) return e;
+    if constexpr (!kBw) {
+        if (a.jvp && (e = big_jvp_products<T>(c, a))) return e;
+    }
     if ((e = big_kkt_core<T>(c, kBw, true))) return e;
     k.stage = 1;
     int rows = a.n > a.m ? a.n : a.m;
@@ -775,6 +805,8 @@ int api_kkt(KktArgs<T>& a, void* stream)
             s.dl_dz = advio(a.dl_dz, o * n, w);
             s.dQ = advio(a.dQ, o * n * n, w); s.dp = advio(a.dp, o * n, w); s.dG = advio(a.dG, o * m * n, w); s.dh = advio(a.dh, o * m, w);
             s.dA = advio(a.dA, o * q * n, w); s.db = advio(a.db, o * q, w);
+            s.tQ = advio(a.tQ, o * a.stQ, w); s.tp = advio(a.tp, o * a.stp, w); s.tG = advio(a.tG, o * a.stG, w);
+            s.th = advio(a.th, o * a.sth, w); s.tA = advio(a.tA, o * a.stA, w); s.tb = advio(a.tb, o * a.stb, w);
             s.status = adv(a.status, o);
             return big_kkt<T, kBw>(s, st);
         });
@@ -810,6 +842,30 @@ int api_kkt(KktArgs<T>& a, void* stream)
         return QPX_ERR_UNSUPPORTED;
     }
     return QPX_ERR_UNSUPPORTED;
+}
+
+// forward mode: the KKT solve of the backward (same d, same kernels: api_kkt<T, false>) with the right-hand side formed from
+// the tangents inside them (KktArgs::jvp)
+template <class T>
+int api_jvp(int io32, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat, const void* lam,
+            const void* slack, const void* nu, const void* tQ, int64_t stQ, const void* tp, int64_t stp, const void* tG,
+            int64_t stG, const void* th, int64_t sth, const void* tA, int64_t stA, const void* tb, int64_t stb, void* dzhat,
+            void* dlam, void* dnu, void* dslack, int refine, const void* Q, int64_t sQ, const void* G, int64_t sG,
+            const void* A, int64_t sA, int32_t* status, void* stream)
+{
+    // (kkt_jvp_rhs holds n <= 256 columns per lane in four slots: the thread-grid / tile sizes have n < 208)
+    if (!use_big(n, m, q, sizeof(T)) && n > 4 * kWave) return QPX_ERR_UNSUPPORTED;
+    KktArgs<T> a{};
+    a.io32 = io32;
+    a.B = B; a.n = n; a.m = m; a.q = q; a.fac = (T*)factors; a.fac_stride = (size_t)sfac;
+    a.zhat = (const T*)zhat; a.lam = (const T*)lam; a.slack = (const T*)slack; a.nu = (const T*)nu;
+    a.jvp = 1;
+    a.tQ = (const T*)tQ; a.tp = (const T*)tp; a.tG = (const T*)tG; a.th = (const T*)th; a.tA = (const T*)tA; a.tb = (const T*)tb;
+    a.stQ = stQ; a.stp = stp; a.stG = stG; a.sth = sth; a.stA = stA; a.stb = stb;
+    a.dx = (T*)dzhat; a.dz = (T*)dlam; a.dy = (T*)dnu; a.ds = (T*)dslack;
+    a.status = status;
+    a.refine = refine; a.Q = (const T*)Q; a.G = (const T*)G; a.A = (const T*)A; a.sQ = sQ; a.sG = sG; a.sA = sA;
+    return api_kkt<T, false>(a, stream);
 }
 
 // the finishing stage: every family has it (thread-grid / tile kernels: one kernel, the blob's register image of R decides the
@@ -1071,6 +1127,24 @@ int qpx_backward(int dtype, int B, int n, int m, int q, void* factors, int64_t s
     a.dx = (float*)dx; a.dz = (float*)dz; a.dy = (float*)dy;
     a.refine = refine; a.Q = (const float*)Q; a.G = (const float*)G; a.A = (const float*)A; a.sQ = sQ; a.sG = sG; a.sA = sA;
     return qpx::api_kkt<float, true>(a, stream);
+}
+
+int qpx_jvp(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat, const void* lam,
+            const void* slack, const void* nu, const void* tQ, int64_t stQ, const void* tp, int64_t stp, const void* tG,
+            int64_t stG, const void* th, int64_t sth, const void* tA, int64_t stA, const void* tb, int64_t stb, void* dzhat,
+            void* dlam, void* dnu, void* dslack, int refine, const void* Q, int64_t sQ, const void* G, int64_t sG,
+            const void* A, int64_t sA, int32_t* status, qpx_stream_t stream)
+{
+    const int e = qpx::check_dims(dtype, B, n, m, q);
+    if (e) return e;
+    if (!factors || !zhat || !lam || !slack || !dzhat || (q > 0 && !nu)) return QPX_ERR_ARG;
+    if (refine < 0) return QPX_ERR_ARG;
+    if (refine > 0 && !qpx_refine_supported(dtype, n, m, q)) return QPX_ERR_UNSUPPORTED;
+    if (dtype != QPX_F32)
+        return qpx::api_jvp<double>(dtype == QPX_F32_WIDE, B, n, m, q, factors, sfac, zhat, lam, slack, nu, tQ, stQ, tp, stp, tG, stG,
+                                    th, sth, tA, stA, tb, stb, dzhat, dlam, dnu, dslack, refine, Q, sQ, G, sG, A, sA, status, stream);
+    return qpx::api_jvp<float>(0, B, n, m, q, factors, sfac, zhat, lam, slack, nu, tQ, stQ, tp, stp, tG, stG, th, sth, tA, stA,
+                               tb, stb, dzhat, dlam, dnu, dslack, refine, Q, sQ, G, sG, A, sA, status, stream);
 }
 
 int qpx_polish_supported(int dtype, int n, int m, int q)

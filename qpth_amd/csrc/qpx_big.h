@@ -686,6 +686,9 @@ template <class T> struct BigGemvArgs {
     T* y; size_t sy;
     T alpha, beta;
     const int* ctrl; size_t sctrl; int check_stop;
+    // forward mode's tangent products (qpx_jvp): M is the CALLER's row-major rows x cols array (ld = cols, no padded blocks),
+    // read within its logical extent; m32: ... and it is float32 (T = double, QPX_F32_WIDE)
+    int dense = 0, m32 = 0;
 };
 // LDS: the vector x (up to 1 024 elements) + 4 x 64 partial sums
 // (sized by the vector there is: eight blocks up to 512 -- the measured footprint --, sixteen beyond)
@@ -694,9 +697,65 @@ QPX_LAYOUT_HD size_t big_gemv_lds_elems(int nx) { return (size_t)big_gemv_x_bloc
 #ifndef QPX_BIG_GEMV_ROWS
 #define QPX_BIG_GEMV_ROWS 4          // rows a wave works on at once (x two column blocks: loads in flight per lane)
 #endif
+// The same products on a caller's row-major matrix (BigGemvArgs::dense): same grid, same LDS (x staged, 4 x 64 partial sums).
+// Rows: a wave takes four at a time, its lanes stride over the columns (coalesced), one wave reduction per row; columns:
+// lane = output column, the rows dealt over the waves, the waves' sums met in LDS.  Every read is inside rows x cols.
+template <class T> QPX_DEV void big_gemv_dense(const Block& b, const BigGemvArgs<T>& a, int qp, int chunk, T* lds)
+{
+    const In<T> M(a.M, (size_t)qp * a.sM, a.m32);
+    const T* x = a.x + (size_t)qp * a.sx;
+    const T* y0 = a.y0 ? a.y0 + (size_t)qp * a.sy0 : nullptr;
+    T* y = a.y + (size_t)qp * a.sy;
+    const int lane = b.lane(), w = b.uniform(b.wave()), nw = b.nwaves();
+    const int nx = a.trans ? a.rows : a.cols, nxp = (nx + kBB - 1) / kBB * kBB;
+    const size_t ld = (size_t)a.cols;
+    T* xl = lds;
+    T* part = lds + big_gemv_x_blocks(nx) * kBB;
+    for (int i = b.tid; i < nxp; i += b.nt) xl[i] = i < nx ? x[i] : T(0);
+    b.sync();
+    if (!a.trans) {
+        constexpr int RB = 4;
+        const int rend = (chunk + 1) * kBB < a.rows ? (chunk + 1) * kBB : a.rows;
+        for (int r0 = chunk * kBB + w * RB; r0 < rend; r0 += nw * RB) {
+            T acc[RB];
+#pragma unroll
+            for (int u = 0; u < RB; ++u) acc[u] = T(0);
+            for (int c = lane; c < a.cols; c += kWave) {
+                const T xc = xl[c];
+#pragma unroll
+                for (int u = 0; u < RB; ++u)
+                    if (r0 + u < rend) acc[u] = fma_(M[(size_t)(r0 + u) * ld + c], xc, acc[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < RB; ++u) acc[u] = wave_sum(b, acc[u]);
+            if (lane == 0) {
+#pragma unroll
+                for (int u = 0; u < RB; ++u)
+                    if (r0 + u < rend) y[r0 + u] = fma_(a.alpha, acc[u], y0 ? a.beta * y0[r0 + u] : T(0));
+            }
+        }
+    } else {
+        const int j = chunk * kBB + lane;
+        T acc = T(0);
+        if (j < a.cols)
+            for (int i = w; i < a.rows; i += nw) acc = fma_(M[(size_t)i * ld + j], xl[i], acc);
+        part[w * kWave + lane] = acc;
+        b.sync();
+        if (w == 0 && j < a.cols) {
+            T s = T(0);
+            for (int ww = 0; ww < nw; ++ww) s += part[ww * kWave + lane];
+            y[j] = fma_(a.alpha, s, y0 ? a.beta * y0[j] : T(0));
+        }
+    }
+}
+
 template <class T> QPX_DEV void big_gemv_body(const Block& b, const BigGemvArgs<T>& a, int qp, int chunk, T* lds)
 {
     if (a.check_stop && a.ctrl && (a.ctrl + (size_t)qp * a.sctrl)[bcStop]) return;
+    if (a.dense) {
+        big_gemv_dense<T>(b, a, qp, chunk, lds);
+        return;
+    }
     const T* M = a.M + (size_t)qp * a.sM;
     const T* x = a.x + (size_t)qp * a.sx;
     const T* y0 = a.y0 ? a.y0 + (size_t)qp * a.sy0 : nullptr;
@@ -1184,6 +1243,11 @@ template <class T> struct BigKktArgs {
     int* status;
     int q; const T *ry, *nu; T *dy, *dA, *db;
     int io32;                             // T = double: every array but `fac` is float32 (QPX_F32_WIDE)
+    // forward mode (qpx_jvp), stage 0: vD = 1/d (the backward's d), vU = tp, vRH = th, vBQ = -tb, and zhat, lam, nu copied into
+    // bvZ, bvS, bvY (element type: what the tangent mat-vecs read) -- the mat-vecs behind it add the tangents' products
+    int jvp = 0;
+    const T *tp = nullptr, *th = nullptr, *tb = nullptr;
+    long long stp = 0, sth = 0, stb = 0;
 };
 template <class T> QPX_DEV void big_kkt_body(const Block& b, const BigKktArgs<T>& a, int qp, int chunk)
 {
@@ -1194,6 +1258,30 @@ template <class T> QPX_DEV void big_kkt_body(const Block& b, const BigKktArgs<T>
     T *vD = F + L.v(bvD), *vRH = F + L.v(bvRH), *vU = F + L.v(bvU), *vX = F + L.v(bvX), *vW = F + L.v(bvW);
     T *vBQ = F + L.v(bvBQ), *vNU = F + L.v(bvNU);
     const In<T> rsg(a.backward ? nullptr : a.rs, (size_t)qp * m, io32);
+    if (a.stage == 0 && a.jvp) {
+        const In<T> zg(a.zhat, (size_t)qp * n, io32), lg(a.lam, (size_t)qp * m, io32), sg(a.slack, (size_t)qp * m, io32);
+        const In<T> ng(q > 0 ? a.nu : nullptr, (size_t)qp * q, io32);
+        const In<T> tpg(a.tp, (size_t)qp * a.stp, io32), thg(a.th, (size_t)qp * a.sth, io32), tbg(q > 0 ? a.tb : nullptr, (size_t)qp * a.stb, io32);
+        T *vZ = F + L.v(bvZ), *vS = F + L.v(bvS), *vY = F + L.v(bvY);
+        for (int i = b.tid; i < L.VP; i += b.nt) {
+            T dinv = T(1);
+            if (i < m) {
+                const T l = lg[i], sl = sg[i];
+                dinv = T(1) / (((l < T(1e-8)) ? T(1e-8) : l) / ((sl < T(1e-8)) ? T(1e-8) : sl));        // qp.py:148, as the backward
+            }
+            vD[i] = dinv;
+            vRH[i] = (i < m && thg) ? thg[i] : T(0);
+            vU[i] = (i < n && tpg) ? tpg[i] : T(0);
+            vW[i] = T(0);
+            vBQ[i] = (i < q && tbg) ? -tbg[i] : T(0);
+            (F + L.v(bvTB))[i] = (F + L.v(bvT1))[i] = vNU[i] = T(0);
+            vZ[i] = i < n ? zg[i] : T(0);
+            vS[i] = i < m ? lg[i] : T(0);
+            vY[i] = i < q ? ng[i] : T(0);
+        }
+        if (b.tid == 0) { ctrl[bcStop] = 0; ctrl[bcFail] &= (QPX_ST_Q_NOT_SPD | QPX_ST_A_RANK); }
+        return;
+    }
     if (a.stage == 0) {
         const In<T> rxg(a.backward ? a.dl_dz : a.rx, (size_t)qp * n, io32), rzg(a.backward ? nullptr : a.rz, (size_t)qp * m, io32);
         const In<T> ryg((!a.backward && q > 0) ? a.ry : nullptr, (size_t)qp * q, io32), dg(a.backward ? nullptr : a.d, (size_t)qp * m, io32);

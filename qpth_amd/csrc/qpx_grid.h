@@ -1309,6 +1309,103 @@ QPX_DEV void ipm_grid_body(const Block& b, const IpmArgs<T>& a, int qp, T* lds)
 }
 
 // ------------------------------------------------------------------------------------------
+// Forward mode (qpx_jvp): the right-hand side of the tangent KKT solve at the forward's solution, in kkt_mat_role's
+// variables -- vD = 1/d with the backward's d (qp.py:148), vRX = rx, vRH = rs/d - rz = th - tG zhat, vRY = ry -- from
+//   rx = 1/2 (tQ + tQ^T) zhat + tp + tG^T lam + tA^T nu,   rz = tG zhat - th,   ry = tA zhat - tb.
+// ONE pass over each tangent matrix gives both of its products: a wave takes four rows at a time, its lanes the columns;
+// the row dots (tM zhat) are wave reductions, the column sums (tM^T y) stay in per-lane double accumulators across all three
+// matrices and meet across the waves once, at the end.  Double accumulation whatever T is (as the refinement's residuals);
+// reads through In<T> (float32 tangents under QPX_F32_WIDE).  zhat, lam, nu are staged in vZH, vLM, vNU.  Runs before R's
+// image is loaded, while the tile registers are free.  n <= 256 (four column slots; the thread-grid / tile sizes have n < 208).
+template <class T, class Mat>
+QPX_DEV void kkt_jvp_rhs(const Block& b, const KktArgs<T>& a, int qp, T* vD, T* vRX, T* vRY, T* vRH, T* vZH, T* vLM, T* vNU)
+{
+    constexpr int M8 = Mat::MP, NT = Mat::NT, RB = 4, CS = 4;
+    const int n = a.n, m = a.m, q = a.q, io32 = a.io32;
+    const In<T> zg(a.zhat, (size_t)qp * n, io32), lg(a.lam, (size_t)qp * m, io32), sg(a.slack, (size_t)qp * m, io32);
+    const In<T> ng(q > 0 ? a.nu : nullptr, (size_t)qp * q, io32);
+    const In<T> tpg(a.tp, (size_t)qp * a.stp, io32), thg(a.th, (size_t)qp * a.sth, io32);
+    const In<T> tbg(q > 0 ? a.tb : nullptr, (size_t)qp * a.stb, io32);
+    for (int i = b.tid; i < n; i += NT) {
+        vZH[i] = zg[i];
+        vRX[i] = tpg ? tpg[i] : T(0);
+    }
+    for (int i = b.tid; i < q; i += NT) {
+        vNU[i] = ng[i];
+        vRY[i] = tbg ? -tbg[i] : T(0);
+    }
+    for (int i = b.tid; i < M8; i += NT) {
+        T dinv = T(1), rhs = T(0), l = T(0);
+        if (i < m) {
+            const T sl = sg[i];
+            l = lg[i];
+            const T d = ((l < T(1e-8)) ? T(1e-8) : l) / ((sl < T(1e-8)) ? T(1e-8) : sl);      // qp.py:148, as the backward
+            dinv = T(1) / d;
+            rhs = thg ? thg[i] : T(0);
+        }
+        vD[i] = dinv;
+        vRH[i] = rhs;
+        vLM[i] = l;
+    }
+    Mat::sync(b);
+    const int lane = b.lane(), w = b.uniform(b.wave()), nw = b.nwaves();
+    double col[CS] = {0.0, 0.0, 0.0, 0.0};           // sc * tM^T y over this wave's rows, every matrix
+    // rows x n tangent: out[r] += sr * (tM zhat)[r];  col += sc * tM^T y
+    auto pass = [&](const T* base, long long stride, int rows, const T* y, double sc, T* out, double sr) {
+        const In<T> M(base, (size_t)qp * stride, io32);
+        if (!M) return;
+        double xv[CS];
+#pragma unroll
+        for (int s = 0; s < CS; ++s) {
+            const int c = lane + kWave * s;
+            xv[s] = c < n ? (double)vZH[c] : 0.0;
+        }
+        for (int r0 = w * RB; r0 < rows; r0 += nw * RB) {
+            double acc[RB];
+#pragma unroll
+            for (int u = 0; u < RB; ++u) {
+                const int r = r0 + u;
+                acc[u] = 0.0;
+                if (r < rows) {
+                    const double yr = sc * (double)y[r];
+#pragma unroll
+                    for (int s = 0; s < CS; ++s) {
+                        const int c = lane + kWave * s;
+                        if (c < n) {
+                            const double v = (double)M[(size_t)r * n + c];
+                            acc[u] = fma_(v, xv[s], acc[u]);
+                            col[s] = fma_(v, yr, col[s]);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < RB; ++u) acc[u] = wave_sum(b, acc[u]);
+            if (lane == 0) {
+#pragma unroll
+                for (int u = 0; u < RB; ++u)
+                    if (r0 + u < rows) out[r0 + u] = (T)((double)out[r0 + u] + sr * acc[u]);
+            }
+        }
+    };
+    pass(a.tQ, a.stQ, n, vZH, 0.5, vRX, 0.5);            // rx += 1/2 tQ zhat (rows) + 1/2 tQ^T zhat (columns)
+    pass(a.tG, a.stG, m, vLM, 1.0, vRH, -1.0);           // rH -= tG zhat;  rx += tG^T lam
+    if (q > 0) pass(a.tA, a.stA, q, vNU, 1.0, vRY, 1.0); // ry += tA zhat;  rx += tA^T nu
+    // the waves' column sums into rx one wave after the other (the first barrier also orders the row dots of tQ before them)
+    for (int ww = 0; ww < nw; ++ww) {
+        Mat::sync(b);
+        if (w == ww) {
+#pragma unroll
+            for (int s = 0; s < CS; ++s) {
+                const int c = lane + kWave * s;
+                if (c < n) vRX[c] = (T)((double)vRX[c] + col[s]);
+            }
+        }
+    }
+    Mat::sync(b);
+}
+
+// ------------------------------------------------------------------------------------------
 // factor_kkt + solve_kkt for arbitrary right-hand sides and QPFunctionFn.backward on the
 // format-3 blob (see kkt_body for the reference citations):
 //   dz = -T^-1 (M rx + W ry + rs/d - rz),  dx = -K rx - M^T dz - N ry,
@@ -1345,8 +1442,20 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
     const In<T> ryg((!kBackward && q > 0) ? a.ry : nullptr, (size_t)qp * q, io32);
     const In<T> lamg(kBackward ? a.lam : nullptr, (size_t)qp * m, io32), slg(kBackward ? a.slack : nullptr, (size_t)qp * m, io32);
     const In<T> dg(kBackward ? nullptr : a.d, (size_t)qp * m, io32);
+    bool jvp = false;                                  // forward mode (qpx_jvp): never in the backward's instantiation
+    if constexpr (!kBackward) jvp = a.jvp != 0;
     QPX_PROF_INIT
 
+    if (jvp) {
+        kkt_jvp_rhs<T, Mat>(b, a, qp, vD, vRX, vRY, vRH, vZH, vLM, vNU);
+        if (a.refine > 0) {
+            // the refinement below re-forms its residuals from the right-hand side: kept where zhat, lam and nu were (dead now)
+            for (int i = b.tid; i < n; i += NT) vZH[i] = vRX[i];
+            for (int i = b.tid; i < M8; i += NT) vLM[i] = vRH[i];
+            for (int i = b.tid; i < q; i += NT) vNU[i] = vRY[i];
+            Mat::sync(b);
+        }
+    } else {
     for (int i = b.tid; i < n; i += NT) vRX[i] = rxg ? rxg[i] : T(0);
     for (int i = b.tid; i < q; i += NT) vRY[i] = ryg ? ryg[i] : T(0);
     for (int i = b.tid; i < M8; i += NT) {
@@ -1366,6 +1475,7 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
         vRH[i] = rhs;
     }
     Mat::sync(b);
+    }
     // One application of the condensed KKT inverse: inputs rX (n), rY (q) and rH = rs/d - rz (M8),
     //   oZ = -T^-1 (rH + M rX + W rY),  oX = -K rX - M^T oZ - N rY,  oY = S11^-1 rY - N^T rX - W^T oZ   (rH is overwritten)
     // in two halves: the products with rX, which need no factor, and the rest.  (r4) Both products at once -- rH += M rX
@@ -1450,10 +1560,11 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
         const T* Gg = a.G + (size_t)qp * a.sG;
         const T* Ag = (q > 0 && a.A) ? a.A + (size_t)qp * a.sA : nullptr;
         for (int it = 0; it < a.refine; ++it) {
-            for (int i = b.tid; i < n; i += NT) vRX[i] = rxg ? rxg[i] : T(0);
-            for (int i = b.tid; i < q; i += NT) vRY[i] = ryg ? ryg[i] : T(0);
+            // (forward mode: rx, ry and rs/d - rz as formed from the tangents, kept in vZH, vNU, vLM; rs = 0 there)
+            for (int i = b.tid; i < n; i += NT) vRX[i] = jvp ? vZH[i] : (rxg ? rxg[i] : T(0));
+            for (int i = b.tid; i < q; i += NT) vRY[i] = jvp ? vNU[i] : (ryg ? ryg[i] : T(0));
             for (int i = b.tid; i < M8; i += NT)     // -(ds + rz): the part of -resz that needs no matrix
-                vRH[i] = (i < m) ? -((-(rsg ? rsg[i] : T(0)) - vDZ[i]) * vD[i] + (rzg ? rzg[i] : T(0))) : T(0);
+                vRH[i] = (i < m) ? (jvp ? vDZ[i] * vD[i] + vLM[i] : -((-(rsg ? rsg[i] : T(0)) - vDZ[i]) * vD[i] + (rzg ? rzg[i] : T(0)))) : T(0);
             Mat::sync(b);
             // residuals accumulate in double whatever T is: fixed-precision refinement cannot improve the forward
             // error of an ill-conditioned solve (cond(Q) ~ 1e6 on the benchmark generator), mixed precision can
@@ -1477,12 +1588,13 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
         }
     }
     if (!kBackward) {
+        // (dz, ds, dy: NULL only in forward mode -- qpx_jvp's tangents of lam, s and nu are optional)
         for (int i = b.tid; i < n; i += NT) put_(a.dx, io32, (size_t)qp * n + i, vDX[i]);
         for (int i = b.tid; i < m; i += NT) {
-            put_(a.dz, io32, (size_t)qp * m + i, vDZ[i]);
-            put_(a.ds, io32, (size_t)qp * m + i, (-(rsg ? rsg[i] : T(0)) - vDZ[i]) * vD[i]);
+            if (a.dz) put_(a.dz, io32, (size_t)qp * m + i, vDZ[i]);
+            if (a.ds) put_(a.ds, io32, (size_t)qp * m + i, (-(rsg ? rsg[i] : T(0)) - vDZ[i]) * vD[i]);
         }
-        for (int i = b.tid; i < q; i += NT) put_(a.dy, io32, (size_t)qp * q + i, vDY[i]);
+        if (a.dy) for (int i = b.tid; i < q; i += NT) put_(a.dy, io32, (size_t)qp * q + i, vDY[i]);
         return;
     }
     // ---- gradients (qp.py:157-173); a NULL output = that gradient is not wanted (ctx.needs_input_grad)

@@ -149,6 +149,12 @@ template <class T> struct KktArgs {
     const T *Q, *G, *A;
     long long sQ, sG, sA;
     int io32 = 0;                         // T = double only: every array but `fac` is float32 (QPX_F32_WIDE; refine = 0)
+    // forward mode (qpx_jvp, kBackward = false only): d from lam / slack as in the backward, the right-hand side formed from
+    // the tangents at (zhat, lam, nu) -- rx = 1/2 (tQ + tQ^T) zhat + tp + tG^T lam + tA^T nu, rs = 0, rz = tG zhat - th,
+    // ry = tA zhat - tb --; outputs dx = dzhat, dz = dlam, ds = dslack, dy = dnu (any but dx may be NULL); d, rx .. ry unused
+    int jvp = 0;
+    const T *tQ = nullptr, *tp = nullptr, *tG = nullptr, *th = nullptr, *tA = nullptr, *tb = nullptr;   // NULL = zero
+    long long stQ = 0, stp = 0, stG = 0, sth = 0, stA = 0, stb = 0;        // batch strides in elements (0 = shared)
 };
 
 // The finishing stage (qpx_polish, include/qpx.h): iterations of the reference's loop in the ORIGINAL variables

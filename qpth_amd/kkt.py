@@ -328,6 +328,35 @@ a non-zero diagonal.
                            "(qpx_polish_supported).  float32 tensors run in float64 arithmetic by default (refine=None)"
                            % (self.n, self.m, self.q))
 
+    # -- QPFunctionFn.jvp: forward mode ---------------------------------------------------------
+    def jvp(self, zhat, lam, slacks, nu, tangents, refine=0, want_duals=False):
+        """The tangent of the solution along `tangents` = (tQ, tp, tG, th, tA, tb) -- each None / empty (zero) or of its
+        parameter's shape, batched, batch-1 or shared -- at the forward's (zhat, lam, slacks, nu): ONE KKT solve with the
+        matrix the backward factors (d = clamp(lam) / clamp(slacks), qp.py:148), its right-hand side formed from the tangents
+        inside the kernel (qpx_jvp, include/qpx.h).  Returns z' (B, n); want_duals: (z', lam', nu').  No host sync."""
+        B, n, m, q = self.B, self.n, self.m, self.q
+        dt, dev = self.dtype, self.device
+        ts = []
+        for X, shape, what in zip(tangents, ((n, n), (n,), (m, n), (m,), (q, n), (q,)), ("Q", "p", "G", "h", "A", "b")):
+            if X is None or X.nelement() == 0 or (q == 0 and what in ("A", "b")):
+                ts.append(None)
+                continue
+            if X.dtype != dt or X.device != dev:
+                raise RuntimeError("qpth_amd: the tangent of %s is %s on %s, the factors were built for %s on %s"
+                                   % (what, X.dtype, X.device, dt, dev))
+            if tuple(X.shape) not in (shape, (1,) + shape, (B,) + shape):
+                raise RuntimeError("qpth_amd: the tangent of %s has shape %s, expected %s, %s or %s"
+                                   % (what, tuple(X.shape), shape, (1,) + shape, (B,) + shape))
+            ts.append(X)
+        dz = torch.empty(B, n, dtype=dt, device=dev)
+        dl = torch.empty(B, m, dtype=dt, device=dev) if want_duals else None
+        dn = torch.empty(B, q, dtype=dt, device=dev) if (want_duals and q) else None
+        with self._knob():
+            self.lib.jvp(B, n, m, q, self.blob, self.sfac, self._vec(zhat, n, "zhat"), self._vec(lam, m, "lam"),
+                         self._vec(slacks, m, "slacks"), self._vec(nu, q, "nu"), *ts, dz, self.status, dlam=dl, dnu=dn,
+                         refine=refine, Q=self.Q, G=self.G, A=self.A, wide=self.wide)
+        return (dz, dl, dn) if want_duals else dz
+
     # -- QPFunctionFn.backward (qp.py:127-182) ------------------------------------------------
     def backward(self, zhat, lam, slacks, nu, dl_dz, want=(True,) * 6, shared=(False,) * 6, refine=0):
         """Gradients (dQ, dp, dG, dh, dA, db) for the parameters `want` asks for (ctx.needs_input_grad;

@@ -8,6 +8,8 @@ in all six parameters.  Any subset of the parameters may be un-batched; an empty
 means "no such constraint" (qp.py:58-61).  The forward runs two HIP kernels
 (pre_factor_kkt, PDIPM loop), the backward one (factor_kkt + solve_kkt + gradient outer
 products); state crosses from forward to backward on ctx exactly as in the reference.
+Forward mode (torch.autograd.forward_ad, which the reference does not support) is one more launch: QPFunctionFn.jvp solves
+the backward's KKT system with the right-hand side formed from the input tangents (qpx_jvp).
 """
 from enum import Enum
 
@@ -111,7 +113,23 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                 assert False
 
             ctx.save_for_backward(zhats, Q_, p_, G_, h_, A_, b_)
+            # forward mode reads no saved_tensors: zhat as an attribute beside lam, s, nu (detached: no cycle through the
+            # output's grad_fn), and on the external-solver path the matrices the factors are rebuilt from
+            ctx.zhat = zhats.detach()
+            ctx.QGA = (Q.detach(), G.detach(), A.detach(), nBatch) if ctx.fac is None else None
             return zhats
+
+        @staticmethod
+        def jvp(ctx, dQ, dp, dG, dh, dA, db):
+            # forward mode: z' solves the backward's KKT system (same d, same factors) with the right-hand side formed from
+            # the tangents on the device -- one launch, no host sync.  A None / empty tangent is zero.
+            fac = ctx.fac
+            if fac is None:                                          # external solver: the factors as backward builds them
+                Q, G, A, nBatch = ctx.QGA
+                fac = KKTFactors.build(Q, G, A, nBatch)
+                fac.raise_on_failure(check_Q_spd)
+            return fac.jvp(ctx.zhat, ctx.lams, ctx.slacks, ctx.nus, (dQ, dp, dG, dh, dA, db),
+                           refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0)
 
         @staticmethod
         def backward(ctx, dl_dzhat):
