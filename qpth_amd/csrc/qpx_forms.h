@@ -1,0 +1,40 @@
+// qpx_forms.h -- which template instantiation ("form") of every launcher family exists: one X-macro list per family.
+// The kernel translation units (qpx_hip_kernels.hip) instantiate from these lists and the dispatcher (qpx_api.inc, which
+// includes this header itself) picks from them, on the GPU and in the host-thread emulator of the test tree alike: a new
+// form is one entry here plus the rule in qpx_api.inc that picks it.  The order of a list is the order of the kernels in
+// the code object.
+#pragma once
+#include <type_traits>
+
+namespace qpx {
+
+// The wave-0 phases of the large-QP family (launch_big_phase / _solve / _diag) hold a vector of the padded nineq in NS
+// slots of 64 lanes: f(std::integral_constant<int, NS>) for the smallest of 1, 2, 4, 8, 16 that covers `ns` = big_pad(m) / kWave
+template <class F> inline int big_ns_form(int ns, F&& f)
+{
+    if (ns <= 1) return f(std::integral_constant<int, 1>{});
+    if (ns <= 2) return f(std::integral_constant<int, 2>{});
+    if (ns <= 4) return f(std::integral_constant<int, 4>{});
+    if (ns <= 8) return f(std::integral_constant<int, 8>{});
+    return f(std::integral_constant<int, 16>{});
+}
+
+}  // namespace qpx
+
+// thread-grid kernels: (blocks of 16 -- of 8 in the one-wave grid -- per side), (blocks, slots of 64 columns)
+#define QPX_FORMS_SWEEP(X) X(1) X(2) X(4) X(7) X(8) X(10) X(13)
+#define QPX_FORMS_IPM_GRID(X) \
+    X(1, 1) X(1, 2) X(1, 4) X(2, 1) X(2, 2) X(2, 4) X(4, 1) X(4, 2) X(4, 4) X(7, 2) X(7, 4) X(10, 4) X(13, 4)
+#define QPX_FORMS_IPM_GRID8(X) X(2, 1) X(2, 2) X(4, 1) X(4, 2) X(8, 1) X(8, 2) X(13, 2)
+#define QPX_FORMS_KKT_GRID(X) X(1) X(2) X(4) X(7) X(10) X(13)                 // each as the KKT solve and as the backward
+#define QPX_FORMS_POLISH_GRID(X) X(1) X(2) X(4) X(7) X(10) X(13)
+// matrix-core tile kernels, f64: (tile rows, waves per QP, [slots,] chain-wave form)
+#define QPX_FORMS_IPM_TILE(X)                                                                                    \
+    X(1, 1, 1, false) X(1, 1, 2, false) X(1, 1, 4, false) X(2, 1, 1, false) X(2, 1, 2, false) X(2, 1, 4, false)  \
+    X(4, 1, 1, false) X(4, 1, 2, false) X(4, 1, 4, false) X(4, 2, 1, false) X(4, 2, 2, false) X(4, 2, 4, false)  \
+    X(7, 2, 2, false) X(7, 2, 4, false)                                                                          \
+    X(7, 4, 2, true) X(7, 4, 4, true) X(4, 4, 1, true) X(4, 4, 2, true) X(4, 4, 4, true)
+#define QPX_FORMS_KKT_TILE(X) \
+    X(1, 1, false) X(2, 1, false) X(4, 1, false) X(4, 2, false) X(7, 2, false) X(7, 4, true) X(4, 4, true)   // each as the KKT solve and as the backward
+#define QPX_FORMS_POLISH_TILE(X) X(1, 1, false) X(2, 1, false) X(4, 1, false) X(4, 4, true) X(7, 4, true)
+#define QPX_FORMS_PREFAC_TILE(X) X(4, false) X(7, false) X(4, true) X(7, true)    // (tile rows of nz + neq, with equalities)

@@ -40,6 +40,14 @@ template <class K> static int allow_big_lds(K kernel, size_t bytes, BigLdsFlags&
     if (tracked) flags.done[dev] = true;   // only after success; idempotent, so a benign race between host threads is harmless
     return QPX_OK;
 }
+// every launcher: the opt-in (one set of flags per kernel instantiation K), the launch, its error code
+template <auto K, class... Args> static int launch_kernel(dim3 grid, int threads, size_t lds_bytes, void* stream, const Args&... args)
+{
+    static BigLdsFlags big_lds_enabled;
+    if (allow_big_lds(K, lds_bytes, big_lds_enabled)) return QPX_ERR_LAUNCH;
+    hipLaunchKernelGGL(K, grid, dim3(threads), lds_bytes, (hipStream_t)stream, args...);
+    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
+}
 
 #if QPX_TU_KERNEL == 5
 // (at least two workgroups per CU -- <= 256 registers -- at every size: the largest instantiation holds 91 matrix entries per thread)
@@ -51,14 +59,10 @@ template <class T, int NBL> __global__ __launch_bounds__(256, 2) void k_sweep(Pr
 }
 template <class T, int NBL> int launch_sweep(const PrefactorArgs<T>& a, size_t lds_bytes, void* stream)
 {
-    auto kern = k_sweep<T, NBL>;
-    static BigLdsFlags big_lds_enabled;
-    if (allow_big_lds(kern, lds_bytes, big_lds_enabled)) return QPX_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(256), lds_bytes, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
+    return launch_kernel<k_sweep<T, NBL>>(dim3(a.B), 256, lds_bytes, stream, a);
 }
-#define QPX_INSTG(NBL) template int launch_sweep<QPX_TU_REAL, NBL>(const PrefactorArgs<QPX_TU_REAL>&, size_t, void*);
-QPX_INSTG(1) QPX_INSTG(2) QPX_INSTG(4) QPX_INSTG(7) QPX_INSTG(8) QPX_INSTG(10) QPX_INSTG(13)
+#define QPX_INST(NBL) template int launch_sweep<QPX_TU_REAL, NBL>(const PrefactorArgs<QPX_TU_REAL>&, size_t, void*);
+QPX_FORMS_SWEEP(QPX_INST)
 #elif QPX_TU_KERNEL == 6
 // two workgroups per CU (2 waves per SIMD) for the common sizes: the two QPs hide each other's
 // barrier / LDS latencies
@@ -70,15 +74,10 @@ template <class T, int NBL, int NS> __global__ __launch_bounds__(256, (NBL <= 7 
 }
 template <class T, int NBL, int NS> int launch_ipm_grid(const IpmArgs<T>& a, size_t lds_bytes, void* stream)
 {
-    auto kern = k_ipm_grid<T, NBL, NS>;
-    static BigLdsFlags big_lds_enabled;
-    if (allow_big_lds(kern, lds_bytes, big_lds_enabled)) return QPX_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(256), lds_bytes, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
+    return launch_kernel<k_ipm_grid<T, NBL, NS>>(dim3(a.B), 256, lds_bytes, stream, a);
 }
-#define QPX_INSTG(NBL, NS) template int launch_ipm_grid<QPX_TU_REAL, NBL, NS>(const IpmArgs<QPX_TU_REAL>&, size_t, void*);
-QPX_INSTG(1, 1) QPX_INSTG(1, 2) QPX_INSTG(1, 4) QPX_INSTG(2, 1) QPX_INSTG(2, 2) QPX_INSTG(2, 4)
-QPX_INSTG(4, 1) QPX_INSTG(4, 2) QPX_INSTG(4, 4) QPX_INSTG(7, 2) QPX_INSTG(7, 4) QPX_INSTG(10, 4) QPX_INSTG(13, 4)
+#define QPX_INST(NBL, NS) template int launch_ipm_grid<QPX_TU_REAL, NBL, NS>(const IpmArgs<QPX_TU_REAL>&, size_t, void*);
+QPX_FORMS_IPM_GRID(QPX_INST)
 #elif QPX_TU_KERNEL == 7
 template <class T, int NBL, bool kBw> __global__ __launch_bounds__(256, (NBL <= 7 ? 2 : 1)) void k_kkt_grid(KktArgs<T> a)
 {
@@ -88,16 +87,12 @@ template <class T, int NBL, bool kBw> __global__ __launch_bounds__(256, (NBL <= 
 }
 template <class T, int NBL, bool kBw> int launch_kkt_grid(const KktArgs<T>& a, size_t lds_bytes, void* stream)
 {
-    auto kern = k_kkt_grid<T, NBL, kBw>;
-    static BigLdsFlags big_lds_enabled;
-    if (allow_big_lds(kern, lds_bytes, big_lds_enabled)) return QPX_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(256), lds_bytes, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
+    return launch_kernel<k_kkt_grid<T, NBL, kBw>>(dim3(a.B), 256, lds_bytes, stream, a);
 }
-#define QPX_INSTG(NBL)                                                                              \
+#define QPX_INST(NBL)                                                                               \
     template int launch_kkt_grid<QPX_TU_REAL, NBL, false>(const KktArgs<QPX_TU_REAL>&, size_t, void*); \
     template int launch_kkt_grid<QPX_TU_REAL, NBL, true>(const KktArgs<QPX_TU_REAL>&, size_t, void*);
-QPX_INSTG(1) QPX_INSTG(2) QPX_INSTG(4) QPX_INSTG(7) QPX_INSTG(10) QPX_INSTG(13)
+QPX_FORMS_KKT_GRID(QPX_INST)
 // the finishing stage (qpx_polish) on the thread grid
 template <class T, int NBL> __global__ __launch_bounds__(256) void k_polish_grid(PolishArgs<T> a)
 {
@@ -107,14 +102,10 @@ template <class T, int NBL> __global__ __launch_bounds__(256) void k_polish_grid
 }
 template <class T, int NBL> int launch_polish_grid(const PolishArgs<T>& a, size_t lds_bytes, void* stream)
 {
-    auto kern = k_polish_grid<T, NBL>;
-    static BigLdsFlags big_lds_enabled;
-    if (allow_big_lds(kern, lds_bytes, big_lds_enabled)) return QPX_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(256), lds_bytes, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
+    return launch_kernel<k_polish_grid<T, NBL>>(dim3(a.B), 256, lds_bytes, stream, a);
 }
 #define QPX_INSTP(NBL) template int launch_polish_grid<QPX_TU_REAL, NBL>(const PolishArgs<QPX_TU_REAL>&, size_t, void*);
-QPX_INSTP(1) QPX_INSTP(2) QPX_INSTP(4) QPX_INSTP(7) QPX_INSTP(10) QPX_INSTP(13)
+QPX_FORMS_POLISH_GRID(QPX_INSTP)
 #elif QPX_TU_KERNEL == 8
 template <class T, int NBL, int NS> __global__ __launch_bounds__(64) void k_ipm_grid8(IpmArgs<T> a)
 {
@@ -124,14 +115,10 @@ template <class T, int NBL, int NS> __global__ __launch_bounds__(64) void k_ipm_
 }
 template <class T, int NBL, int NS> int launch_ipm_grid8(const IpmArgs<T>& a, size_t lds_bytes, void* stream)
 {
-    auto kern = k_ipm_grid8<T, NBL, NS>;
-    static BigLdsFlags big_lds_enabled;
-    if (allow_big_lds(kern, lds_bytes, big_lds_enabled)) return QPX_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(64), lds_bytes, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
+    return launch_kernel<k_ipm_grid8<T, NBL, NS>>(dim3(a.B), 64, lds_bytes, stream, a);
 }
-#define QPX_INSTG(NBL, NS) template int launch_ipm_grid8<QPX_TU_REAL, NBL, NS>(const IpmArgs<QPX_TU_REAL>&, size_t, void*);
-QPX_INSTG(2, 1) QPX_INSTG(2, 2) QPX_INSTG(4, 1) QPX_INSTG(4, 2) QPX_INSTG(8, 1) QPX_INSTG(8, 2) QPX_INSTG(13, 2)
+#define QPX_INST(NBL, NS) template int launch_ipm_grid8<QPX_TU_REAL, NBL, NS>(const IpmArgs<QPX_TU_REAL>&, size_t, void*);
+QPX_FORMS_IPM_GRID8(QPX_INST)
 #elif QPX_TU_KERNEL == 13
 // the finishing stage (qpx_polish) on matrix-core tiles, f64: the forms the dispatcher picks by default
 template <int NBL, int NW, bool CH> __global__ __launch_bounds__(64 * NW, 2) void k_polish_tile(PolishArgs<double> a)
@@ -142,14 +129,10 @@ template <int NBL, int NW, bool CH> __global__ __launch_bounds__(64 * NW, 2) voi
 }
 template <int NBL, int NW, bool CH> int launch_polish_tile(const PolishArgs<double>& a, size_t lds_bytes, void* stream)
 {
-    auto kern = k_polish_tile<NBL, NW, CH>;
-    static BigLdsFlags big_lds_enabled;
-    if (allow_big_lds(kern, lds_bytes, big_lds_enabled)) return QPX_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(64 * NW), lds_bytes, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
+    return launch_kernel<k_polish_tile<NBL, NW, CH>>(dim3(a.B), 64 * NW, lds_bytes, stream, a);
 }
-#define QPX_INSTPT(NBL, NW, CH) template int launch_polish_tile<NBL, NW, CH>(const PolishArgs<double>&, size_t, void*);
-QPX_INSTPT(1, 1, false) QPX_INSTPT(2, 1, false) QPX_INSTPT(4, 1, false) QPX_INSTPT(4, 4, true) QPX_INSTPT(7, 4, true)
+#define QPX_INST(NBL, NW, CH) template int launch_polish_tile<NBL, NW, CH>(const PolishArgs<double>&, size_t, void*);
+QPX_FORMS_POLISH_TILE(QPX_INST)
 #elif QPX_TU_KERNEL == 14
 // pre_factor_kkt on matrix-core tiles (qpx_prefac.h), f64, neq = 0: four waves per QP, two QPs per CU
 template <int NBN, bool kEq> __global__ __launch_bounds__(256, 2) void k_prefac_tile(PrefactorArgs<double> a)
@@ -160,16 +143,10 @@ template <int NBN, bool kEq> __global__ __launch_bounds__(256, 2) void k_prefac_
 }
 template <int NBN, bool kEq> int launch_prefac_tile(const PrefactorArgs<double>& a, size_t lds_bytes, void* stream)
 {
-    auto kern = k_prefac_tile<NBN, kEq>;
-    static BigLdsFlags big_lds_enabled;
-    if (allow_big_lds(kern, lds_bytes, big_lds_enabled)) return QPX_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(256), lds_bytes, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
+    return launch_kernel<k_prefac_tile<NBN, kEq>>(dim3(a.B), 256, lds_bytes, stream, a);
 }
-template int launch_prefac_tile<4, false>(const PrefactorArgs<double>&, size_t, void*);
-template int launch_prefac_tile<7, false>(const PrefactorArgs<double>&, size_t, void*);
-template int launch_prefac_tile<4, true>(const PrefactorArgs<double>&, size_t, void*);
-template int launch_prefac_tile<7, true>(const PrefactorArgs<double>&, size_t, void*);
+#define QPX_INST(NBN, EQ) template int launch_prefac_tile<NBN, EQ>(const PrefactorArgs<double>&, size_t, void*);
+QPX_FORMS_PREFAC_TILE(QPX_INST)
 #elif QPX_TU_KERNEL == 10 || QPX_TU_KERNEL == 11
 // defined below, outside the launcher chain
 #elif QPX_TU_KERNEL == 9
@@ -187,11 +164,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_ipm_tile(IpmArgs<double> a)
 }
 template <int NBL, int NW, int NS, bool CH> int launch_ipm_tile(const IpmArgs<double>& a, size_t lds_bytes, void* stream)
 {
-    auto kern = k_ipm_tile<NBL, NW, NS, CH>;
-    static BigLdsFlags big_lds_enabled;
-    if (allow_big_lds(kern, lds_bytes, big_lds_enabled)) return QPX_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(64 * NW), lds_bytes, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
+    return launch_kernel<k_ipm_tile<NBL, NW, NS, CH>>(dim3(a.B), 64 * NW, lds_bytes, stream, a);
 }
 #ifdef QPX_PANEL_PROF
 // profiling build only: read and reset the panel sub-phase counters (see qpx_tile.h)
@@ -219,27 +192,19 @@ __global__ __launch_bounds__(64 * NW, 2) void k_kkt_tile(KktArgs<double> a)
 }
 template <int NBL, int NW, bool kBw, bool CH> int launch_kkt_tile(const KktArgs<double>& a, size_t lds_bytes, void* stream)
 {
-    auto kern = k_kkt_tile<NBL, NW, kBw, CH>;
-    static BigLdsFlags big_lds_enabled;
-    if (allow_big_lds(kern, lds_bytes, big_lds_enabled)) return QPX_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(64 * NW), lds_bytes, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
+    return launch_kernel<k_kkt_tile<NBL, NW, kBw, CH>>(dim3(a.B), 64 * NW, lds_bytes, stream, a);
 }
 #define QPX_INSTK(NBL, NW, CH)                                                                     \
     template int launch_kkt_tile<NBL, NW, false, CH>(const KktArgs<double>&, size_t, void*);       \
     template int launch_kkt_tile<NBL, NW, true, CH>(const KktArgs<double>&, size_t, void*);
 #if !defined(QPX_TILE_ONLY)
-QPX_INSTK(1, 1, false) QPX_INSTK(2, 1, false) QPX_INSTK(4, 1, false) QPX_INSTK(4, 2, false) QPX_INSTK(7, 2, false)
-QPX_INSTK(7, 4, true) QPX_INSTK(4, 4, true)
+QPX_FORMS_KKT_TILE(QPX_INSTK)
 #endif
 #define QPX_INSTT(NBL, NW, NS, CH) template int launch_ipm_tile<NBL, NW, NS, CH>(const IpmArgs<double>&, size_t, void*);
 #if defined(QPX_TILE_ONLY)
 QPX_INSTT(7, QPX_TILE_ONLY, 2, QPX_TILE_ONLY == 4)
 #else
-QPX_INSTT(1, 1, 1, false) QPX_INSTT(1, 1, 2, false) QPX_INSTT(1, 1, 4, false) QPX_INSTT(2, 1, 1, false) QPX_INSTT(2, 1, 2, false)
-QPX_INSTT(2, 1, 4, false) QPX_INSTT(4, 1, 1, false) QPX_INSTT(4, 1, 2, false) QPX_INSTT(4, 1, 4, false) QPX_INSTT(4, 2, 1, false)
-QPX_INSTT(4, 2, 2, false) QPX_INSTT(4, 2, 4, false) QPX_INSTT(7, 2, 2, false) QPX_INSTT(7, 2, 4, false)
-QPX_INSTT(7, 4, 2, true) QPX_INSTT(7, 4, 4, true) QPX_INSTT(4, 4, 1, true) QPX_INSTT(4, 4, 2, true) QPX_INSTT(4, 4, 4, true)
+QPX_FORMS_IPM_TILE(QPX_INSTT)
 #endif
 #endif
 
@@ -322,89 +287,50 @@ template <class T> __global__ __launch_bounds__(64 * kBigPolWaves) void k_big_po
     const Block b{(int)threadIdx.x, (int)blockDim.x};
     big_polish_body<T>(b, a, (int)blockIdx.x, reinterpret_cast<double*>(qpx_smem));
 }
-template <class K, class A> static int big_launch(K kern, const A& a, int gx, int gy, int threads, size_t lds, void* stream, BigLdsFlags& big_ok)
-{
-    if (allow_big_lds(kern, lds, big_ok)) return QPX_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(threads), lds, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
-}
-template <class T> int launch_big_pack(const BigPackArgs<T>& a, int gy, void* s) { static BigLdsFlags f; return big_launch(k_big_pack<T>, a, a.B, gy, 256, 0, s, f); }
-template <class T> int launch_big_panel(const BigPanelArgs<T>& a, void* s) { static BigLdsFlags f; return big_launch(k_big_panel<T>, a, a.B, 1, 256, big_panel_lds_elems() * sizeof(T), s, f); }
+template <class T> int launch_big_pack(const BigPackArgs<T>& a, int gy, void* s) { return launch_kernel<k_big_pack<T>>(dim3(a.B, gy), 256, 0, s, a); }
+template <class T> int launch_big_panel(const BigPanelArgs<T>& a, void* s) { return launch_kernel<k_big_panel<T>>(dim3(a.B), 256, big_panel_lds_elems() * sizeof(T), s, a); }
 template <class T> int launch_big_gemm(const BigGemmArgs<T>& a, void* s)
 {
-    static BigLdsFlags f2;
     const int ntiles = a.nti * a.ntj, swz = (a.B % 8 == 0 && ntiles > 1 && a.fuse && !a.no_swizzle) ? 1 : 0;   // measured (r02i): the trailing updates gain 3 %, R = Zt Zt^T (half its tiles empty) loses 30 %
     const size_t lds = big_gemm2_lds_elems<T>(a.fuse != 0, a.mirror != 0) * sizeof(T);
-    if (a.fuse) {
-        if (allow_big_lds(k_big_gemm2<T, true>, lds, f2)) return QPX_ERR_LAUNCH;
-        hipLaunchKernelGGL((k_big_gemm2<T, true>), swz ? dim3(a.B * ntiles) : dim3(a.B, ntiles), dim3(256), lds, (hipStream_t)s, a, ntiles, swz);
-    } else {
-        hipLaunchKernelGGL((k_big_gemm2<T, false>), swz ? dim3(a.B * ntiles) : dim3(a.B, ntiles), dim3(256), lds, (hipStream_t)s, a, ntiles, swz);
-    }
-    return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
+    const dim3 grid = swz ? dim3(a.B * ntiles) : dim3(a.B, ntiles);
+    if (a.fuse) return launch_kernel<k_big_gemm2<T, true>>(grid, 256, lds, s, a, ntiles, swz);
+    return launch_kernel<k_big_gemm2<T, false>>(grid, 256, lds, s, a, ntiles, swz);
 }
 template <class T> int launch_big_trsv(const BigTrsvArgs<T>& a, void* s)
 {
-    static BigLdsFlags f;
-    if (a.nb > 8) { static BigLdsFlags f2; return big_launch(k_big_trsv<T, true>, a, a.B, 1, 64 * kTrsvNW, big_trsv_lds_elems(a.nb * kBB) * sizeof(T), s, f2); }
-    return big_launch(k_big_trsv<T, false>, a, a.B, 1, 64 * kTrsvNW, big_trsv_lds_elems(a.nb * kBB) * sizeof(T), s, f);
+    const size_t lds = big_trsv_lds_elems(a.nb * kBB) * sizeof(T);
+    if (a.nb > 8) return launch_kernel<k_big_trsv<T, true>>(dim3(a.B), 64 * kTrsvNW, lds, s, a);
+    return launch_kernel<k_big_trsv<T, false>>(dim3(a.B), 64 * kTrsvNW, lds, s, a);
 }
 template <class T> int launch_big_gemv(const BigGemvArgs<T>& a, void* s)
 {
-    static BigLdsFlags f;
     const int outs = a.trans ? a.cols : a.rows;
-    return big_launch(k_big_gemv<T>, a, a.B, (outs + kBB - 1) / kBB, 256, big_gemv_lds_elems(a.trans ? a.rows : a.cols) * sizeof(T), s, f);
+    return launch_kernel<k_big_gemv<T>>(dim3(a.B, (outs + kBB - 1) / kBB), 256, big_gemv_lds_elems(a.trans ? a.rows : a.cols) * sizeof(T), s, a);
 }
 template <class T> int launch_big_symv(const BigSymvArgs<T>& a, void* s)
 {
-    static BigLdsFlags f;
-    return big_launch(k_big_symv<T>, a, a.B, a.stage == 0 ? a.ld / kBB : 1, 256, big_symv_lds_elems() * sizeof(T), s, f);
+    return launch_kernel<k_big_symv<T>>(dim3(a.B, a.stage == 0 ? a.ld / kBB : 1), 256, big_symv_lds_elems() * sizeof(T), s, a);
 }
-template <class T> int launch_big_vec(const BigVecArgs<T>& a, void* s) { static BigLdsFlags f; return big_launch(k_big_vec<T>, a, a.B, 1, 256, 0, s, f); }
-template <class T> int launch_big_kkt(const BigKktArgs<T>& a, int gy, void* s) { static BigLdsFlags f; return big_launch(k_big_kkt<T>, a, a.B, gy, 256, 0, s, f); }
+template <class T> int launch_big_vec(const BigVecArgs<T>& a, void* s) { return launch_kernel<k_big_vec<T>>(dim3(a.B), 256, 0, s, a); }
+template <class T> int launch_big_kkt(const BigKktArgs<T>& a, int gy, void* s) { return launch_kernel<k_big_kkt<T>>(dim3(a.B, gy), 256, 0, s, a); }
 template <class T> int launch_big_phase(const BigPhaseArgs<T>& a, void* s)
 {
-    static BigLdsFlags f;
-    const int ns = big_pad(a.m) / kWave;
-    switch (ns) {
-    case 1: return big_launch(k_big_phase<T, 1>, a, a.B, 1, 64, 0, s, f);
-    case 2: return big_launch(k_big_phase<T, 2>, a, a.B, 1, 64, 0, s, f);
-    case 3: case 4: return big_launch(k_big_phase<T, 4>, a, a.B, 1, 64, 0, s, f);
-    case 5: case 6: case 7: case 8: return big_launch(k_big_phase<T, 8>, a, a.B, 1, 64, 0, s, f);
-    default: return big_launch(k_big_phase<T, 16>, a, a.B, 1, 64, 0, s, f);
-    }
+    return big_ns_form(big_pad(a.m) / kWave, [&](auto ns) { return launch_kernel<k_big_phase<T, decltype(ns)::value>>(dim3(a.B), 64, 0, s, a); });
 }
 template <class T> int launch_big_solve(const BigSolveArgs<T>& a, void* s)
 {
-    static BigLdsFlags f;
     const size_t lds = big_trsv_lds_elems(a.t.nb * kBB) * sizeof(T);
-    const int ns = big_pad(a.ph.m) / kWave;
-    switch (ns) {
-    case 1: return big_launch(k_big_solve<T, 1>, a, a.t.B, 1, 64 * kTrsvNW, lds, s, f);
-    case 2: return big_launch(k_big_solve<T, 2>, a, a.t.B, 1, 64 * kTrsvNW, lds, s, f);
-    case 3: case 4: return big_launch(k_big_solve<T, 4>, a, a.t.B, 1, 64 * kTrsvNW, lds, s, f);
-    case 5: case 6: case 7: case 8: return big_launch(k_big_solve<T, 8>, a, a.t.B, 1, 64 * kTrsvNW, lds, s, f);
-    default: return big_launch(k_big_solve<T, 16>, a, a.t.B, 1, 64 * kTrsvNW, lds, s, f);
-    }
+    return big_ns_form(big_pad(a.ph.m) / kWave, [&](auto ns) { return launch_kernel<k_big_solve<T, decltype(ns)::value>>(dim3(a.t.B), 64 * kTrsvNW, lds, s, a); });
 }
 template <class T> int launch_big_diag(const BigDiagArgs<T>& a, void* s)
 {
-    static BigLdsFlags f;
     const size_t lds = big_panel_lds_elems() * sizeof(T);
-    const int ns = big_pad(a.ph.m) / kWave;
-    switch (ns) {
-    case 1: return big_launch(k_big_diag<T, 1>, a, a.p.B, 1, 256, lds, s, f);
-    case 2: return big_launch(k_big_diag<T, 2>, a, a.p.B, 1, 256, lds, s, f);
-    case 3: case 4: return big_launch(k_big_diag<T, 4>, a, a.p.B, 1, 256, lds, s, f);
-    case 5: case 6: case 7: case 8: return big_launch(k_big_diag<T, 8>, a, a.p.B, 1, 256, lds, s, f);
-    default: return big_launch(k_big_diag<T, 16>, a, a.p.B, 1, 256, lds, s, f);
-    }
+    return big_ns_form(big_pad(a.ph.m) / kWave, [&](auto ns) { return launch_kernel<k_big_diag<T, decltype(ns)::value>>(dim3(a.p.B), 256, lds, s, a); });
 }
 template <class T> int launch_big_polish(const BigPolishArgs<T>& a, void* s)
 {
-    static BigLdsFlags f;
-    const BigLayout L = big_layout(a.n, a.m, a.q);
-    return big_launch(k_big_polish<T>, a, a.B, 1, 64 * kBigPolWaves, big_polish_lds_doubles(L.VP) * sizeof(double), s, f);
+    return launch_kernel<k_big_polish<T>>(dim3(a.B), 64 * kBigPolWaves, big_polish_lds_doubles(big_layout(a.n, a.m, a.q).VP) * sizeof(double), s, a);
 }
 #define QPX_INSTB(NAME, ARGS) template int NAME<QPX_TU_REAL>(const ARGS<QPX_TU_REAL>&, void*);
 QPX_INSTB(launch_big_polish, BigPolishArgs)

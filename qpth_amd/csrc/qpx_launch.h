@@ -3,8 +3,8 @@
 // -DQPX_TU_KERNEL=... -DQPX_TU_REAL=...) so the build parallelises; the definitions live there.
 #pragma once
 #include <cstddef>
-#include <type_traits>
 
+#include "qpx_forms.h"
 #include "qpx_kernels.h"
 #include "qpx_grid.h"
 #include "qpx_tile.h"
@@ -20,12 +20,13 @@ template <bool V> using Bool = std::integral_constant<bool, V>;
 
 inline size_t lds_budget_bytes() { return kMaxLdsBytes; }
 
+// The forms of each family that are instantiated: qpx_forms.h.
 // thread-grid kernels (qpx_grid.h), 16x16 threads per QP, format-3 blob
 template <class T, int NBL> int launch_sweep(const PrefactorArgs<T>& a, size_t lds_bytes, void* stream);
 template <class T, int NBL, int NS> int launch_ipm_grid(const IpmArgs<T>& a, size_t lds_bytes, void* stream);
 template <int NBN, bool kEq> int launch_prefac_tile(const PrefactorArgs<double>& a, size_t lds_bytes, void* stream);     // pre_factor_kkt on matrix-core tiles (qpx_prefac.h)
-template <int NBL, int NW, int NS, bool CH = false> int launch_ipm_tile(const IpmArgs<double>& a, size_t lds_bytes, void* stream);     // matrix-core tiles, f64, NW waves per QP (CH: chain-wave form)
-template <int NBL, int NW, bool kBw, bool CH = false> int launch_kkt_tile(const KktArgs<double>& a, size_t lds_bytes, void* stream);
+template <int NBL, int NW, int NS, bool CH> int launch_ipm_tile(const IpmArgs<double>& a, size_t lds_bytes, void* stream);     // matrix-core tiles, f64, NW waves per QP (CH: chain-wave form)
+template <int NBL, int NW, bool kBw, bool CH> int launch_kkt_tile(const KktArgs<double>& a, size_t lds_bytes, void* stream);
 template <class T, int NBL, int NS> int launch_ipm_grid8(const IpmArgs<T>& a, size_t lds_bytes, void* stream);   // 8x8 grid = one wave
 template <class T, int NBL, bool kBw> int launch_kkt_grid(const KktArgs<T>& a, size_t lds_bytes, void* stream);
 
@@ -50,7 +51,7 @@ template <class T> int launch_big_phase(const BigPhaseArgs<T>& a, void* stream);
 template <class T> int launch_big_solve(const BigSolveArgs<T>& a, void* stream);
 template <class T> int launch_big_diag(const BigDiagArgs<T>& a, void* stream);
 template <class T> int launch_big_polish(const BigPolishArgs<T>& a, void* stream);      // the finishing stage (qpx_big_polish.h)
-// Side streams for the parts of a batch the large-QP family works on concurrently (qpx_api.inc: big_split).
+// Side streams for the parts of a batch the large-QP family works on concurrently (qpx_big_host.inc: big_split).
 // stream_fork: side[0 .. nside) = streams of the calling host thread's pool, made to wait (event) for everything
 // enqueued on `caller` so far; stream_join: `caller` waits (events) for everything enqueued on them.  Neither
 // synchronises the host -- except that stream_fork checks a side stream ONCE per caller stream (outside stream capture) for

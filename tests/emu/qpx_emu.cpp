@@ -9,11 +9,11 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/qpx.h"
 #include "qpx_platform.h"  // the emulation header: defines QPX_PLATFORM_H, so the HIP one is skipped
+#include "qpx_forms.h"
 #include "qpx_kernels.h"
 #include "qpx_grid.h"
 #include "qpx_tile.h"
@@ -29,9 +29,6 @@
 #endif
 
 namespace qpx {
-
-template <int V> using Int = std::integral_constant<int, V>;
-template <bool V> using Bool = std::integral_constant<bool, V>;
 
 // QPX_EMU_LDS_BYTES shrinks the emulated LDS so that small problems exercise the
 // "matrices stay in the HBM blob" code path.
@@ -296,91 +293,8 @@ template <class Body> static void run_block(int nt, const Body& body)
 }
 #endif
 
-template <class T, int NBL> int launch_sweep(const PrefactorArgs<T>& a, size_t lds_bytes, void*)
-{
-    for (int qp = 0; qp < a.B; ++qp) {
-        std::vector<unsigned char> lds(lds_bytes + QPX_EMU_LDS_SLACK);
-        T* base = reinterpret_cast<T*>(lds.data());
-        run_block(256, [&](const Block& b) { sweep_body<T, NBL>(b, a, qp, base); });
-    }
-    return QPX_OK;
-}
-template <int NBN, bool kEq> int launch_prefac_tile(const PrefactorArgs<double>& a, size_t lds_bytes, void*)
-{
-    for (int qp = 0; qp < a.B; ++qp) {
-        std::vector<unsigned char> lds(lds_bytes + QPX_EMU_LDS_SLACK);
-        double* base = reinterpret_cast<double*>(lds.data());
-        run_block(256, [&](const Block& b) { prefac_tile_body<NBN, kEq>(b, a, qp, base); });
-    }
-    return QPX_OK;
-}
-template <class T, int NBL, int NS> int launch_ipm_grid(const IpmArgs<T>& a, size_t lds_bytes, void*)
-{
-    for (int qp = 0; qp < a.B; ++qp) {
-        std::vector<unsigned char> lds(lds_bytes + QPX_EMU_LDS_SLACK);
-        T* base = reinterpret_cast<T*>(lds.data());
-        run_block(256, [&](const Block& b) { ipm_grid_body<T, 16, NBL, NS>(b, a, qp, base); });
-    }
-    return QPX_OK;
-}
-template <class T, int NBL, int NS> int launch_ipm_grid8(const IpmArgs<T>& a, size_t lds_bytes, void*)
-{
-    for (int qp = 0; qp < a.B; ++qp) {
-        std::vector<unsigned char> lds(lds_bytes + QPX_EMU_LDS_SLACK);
-        T* base = reinterpret_cast<T*>(lds.data());
-        run_block(64, [&](const Block& b) { ipm_grid_body<T, 8, NBL, NS>(b, a, qp, base); });
-    }
-    return QPX_OK;
-}
-template <int NBL, int NW, int NS, bool CH = false> int launch_ipm_tile(const IpmArgs<double>& a, size_t lds_bytes, void*)
-{
-    for (int qp = 0; qp < a.B; ++qp) {
-        std::vector<unsigned char> lds(lds_bytes + QPX_EMU_LDS_SLACK);
-        double* base = reinterpret_cast<double*>(lds.data());
-        run_block(64 * NW, [&](const Block& b) { ipm_tile_body<NBL, NW, NS, CH>(b, a, qp, base); });
-    }
-    return QPX_OK;
-}
-template <int NBL, int NW, bool kBw, bool CH = false> int launch_kkt_tile(const KktArgs<double>& a, size_t lds_bytes, void*)
-{
-    for (int qp = 0; qp < a.B; ++qp) {
-        std::vector<unsigned char> lds(lds_bytes + QPX_EMU_LDS_SLACK);
-        double* base = reinterpret_cast<double*>(lds.data());
-        run_block(64 * NW, [&](const Block& b) { kkt_tile_body<NBL, NW, kBw, CH>(b, a, qp, base); });
-    }
-    return QPX_OK;
-}
-template <class T, int NBL, bool kBw> int launch_kkt_grid(const KktArgs<T>& a, size_t lds_bytes, void*)
-{
-    for (int qp = 0; qp < a.B; ++qp) {
-        std::vector<unsigned char> lds(lds_bytes + QPX_EMU_LDS_SLACK);
-        T* base = reinterpret_cast<T*>(lds.data());
-        run_block(256, [&](const Block& b) { kkt_grid_body<T, 16, NBL, kBw>(b, a, qp, base); });
-    }
-    return QPX_OK;
-}
-
-template <class T, int NBL> int launch_polish_grid(const PolishArgs<T>& a, size_t lds_bytes, void*)
-{
-    for (int qp = 0; qp < a.B; ++qp) {
-        std::vector<unsigned char> lds(lds_bytes + QPX_EMU_LDS_SLACK);
-        T* base = reinterpret_cast<T*>(lds.data());
-        run_block(256, [&](const Block& b) { polish_grid_body<T, 16, NBL>(b, a, qp, base); });
-    }
-    return QPX_OK;
-}
-template <int NBL, int NW, bool CH> int launch_polish_tile(const PolishArgs<double>& a, size_t lds_bytes, void*)
-{
-    for (int qp = 0; qp < a.B; ++qp) {
-        std::vector<unsigned char> lds(lds_bytes + QPX_EMU_LDS_SLACK);
-        double* base = reinterpret_cast<double*>(lds.data());
-        run_block(64 * NW, [&](const Block& b) { polish_mat_body<double, TileMat<NBL, NW, CH>>(b, a, qp, base); });
-    }
-    return QPX_OK;
-}
-
-// the large-QP family: grid (B, gy) of workgroups, one after the other
-template <class F> static void big_grid(int B, int gy, int threads, size_t lds_bytes, const F& body)
+// every launch: a grid (B, gy) of workgroups, one after the other, each over a fresh zero-initialised "LDS"
+template <class F> static int emu_grid(int B, int gy, int threads, size_t lds_bytes, const F& body)
 {
     for (int y = 0; y < gy; ++y)
         for (int qp = 0; qp < B; ++qp) {
@@ -388,97 +302,110 @@ template <class F> static void big_grid(int B, int gy, int threads, size_t lds_b
             unsigned char* base = lds.data();
             run_block(threads, [&](const Block& b) { body(b, qp, y, base); });
         }
+    return QPX_OK;
 }
+// one workgroup per QP, the LDS as the kernel's type
+template <class T, class F> static int emu_per_qp(int B, int threads, size_t lds_bytes, const F& body)
+{
+    return emu_grid(B, 1, threads, lds_bytes, [&](const Block& b, int qp, int, unsigned char* l) { body(b, qp, reinterpret_cast<T*>(l)); });
+}
+
+template <class T, int NBL> int launch_sweep(const PrefactorArgs<T>& a, size_t lds_bytes, void*)
+{
+    return emu_per_qp<T>(a.B, 256, lds_bytes, [&](const Block& b, int qp, T* lds) { sweep_body<T, NBL>(b, a, qp, lds); });
+}
+template <int NBN, bool kEq> int launch_prefac_tile(const PrefactorArgs<double>& a, size_t lds_bytes, void*)
+{
+    return emu_per_qp<double>(a.B, 256, lds_bytes, [&](const Block& b, int qp, double* lds) { prefac_tile_body<NBN, kEq>(b, a, qp, lds); });
+}
+template <class T, int NBL, int NS> int launch_ipm_grid(const IpmArgs<T>& a, size_t lds_bytes, void*)
+{
+    return emu_per_qp<T>(a.B, 256, lds_bytes, [&](const Block& b, int qp, T* lds) { ipm_grid_body<T, 16, NBL, NS>(b, a, qp, lds); });
+}
+template <class T, int NBL, int NS> int launch_ipm_grid8(const IpmArgs<T>& a, size_t lds_bytes, void*)
+{
+    return emu_per_qp<T>(a.B, 64, lds_bytes, [&](const Block& b, int qp, T* lds) { ipm_grid_body<T, 8, NBL, NS>(b, a, qp, lds); });
+}
+template <int NBL, int NW, int NS, bool CH> int launch_ipm_tile(const IpmArgs<double>& a, size_t lds_bytes, void*)
+{
+    return emu_per_qp<double>(a.B, 64 * NW, lds_bytes, [&](const Block& b, int qp, double* lds) { ipm_tile_body<NBL, NW, NS, CH>(b, a, qp, lds); });
+}
+template <int NBL, int NW, bool kBw, bool CH> int launch_kkt_tile(const KktArgs<double>& a, size_t lds_bytes, void*)
+{
+    return emu_per_qp<double>(a.B, 64 * NW, lds_bytes, [&](const Block& b, int qp, double* lds) { kkt_tile_body<NBL, NW, kBw, CH>(b, a, qp, lds); });
+}
+template <class T, int NBL, bool kBw> int launch_kkt_grid(const KktArgs<T>& a, size_t lds_bytes, void*)
+{
+    return emu_per_qp<T>(a.B, 256, lds_bytes, [&](const Block& b, int qp, T* lds) { kkt_grid_body<T, 16, NBL, kBw>(b, a, qp, lds); });
+}
+template <class T, int NBL> int launch_polish_grid(const PolishArgs<T>& a, size_t lds_bytes, void*)
+{
+    return emu_per_qp<T>(a.B, 256, lds_bytes, [&](const Block& b, int qp, T* lds) { polish_grid_body<T, 16, NBL>(b, a, qp, lds); });
+}
+template <int NBL, int NW, bool CH> int launch_polish_tile(const PolishArgs<double>& a, size_t lds_bytes, void*)
+{
+    return emu_per_qp<double>(a.B, 64 * NW, lds_bytes, [&](const Block& b, int qp, double* lds) { polish_mat_body<double, TileMat<NBL, NW, CH>>(b, a, qp, lds); });
+}
+
+// the large-QP family
 template <class T> int launch_big_pack(const BigPackArgs<T>& a, int gy, void*)
 {
-    big_grid(a.B, gy, 256, 0, [&](const Block& b, int qp, int y, unsigned char*) { big_pack_body<T>(b, a, qp, y); });
-    return QPX_OK;
+    return emu_grid(a.B, gy, 256, 0, [&](const Block& b, int qp, int y, unsigned char*) { big_pack_body<T>(b, a, qp, y); });
 }
 template <class T> int launch_big_panel(const BigPanelArgs<T>& a, void*)
 {
-    big_grid(a.B, 1, 256, big_panel_lds_elems() * sizeof(T), [&](const Block& b, int qp, int, unsigned char* l) { big_panel_body<T>(b, a, qp, reinterpret_cast<T*>(l)); });
-    return QPX_OK;
+    return emu_per_qp<T>(a.B, 256, big_panel_lds_elems() * sizeof(T), [&](const Block& b, int qp, T* lds) { big_panel_body<T>(b, a, qp, lds); });
 }
 template <class T> int launch_big_gemm(const BigGemmArgs<T>& a, void*)
 {
-    big_grid(a.B, a.nti * a.ntj, 256, big_gemm2_lds_elems<T>(a.fuse != 0, a.mirror != 0) * sizeof(T), [&](const Block& b, int qp, int y, unsigned char* l) { big_gemm2_body<T, true>(b, a, qp, y, reinterpret_cast<T*>(l)); });
-    return QPX_OK;
+    return emu_grid(a.B, a.nti * a.ntj, 256, big_gemm2_lds_elems<T>(a.fuse != 0, a.mirror != 0) * sizeof(T), [&](const Block& b, int qp, int y, unsigned char* l) { big_gemm2_body<T, true>(b, a, qp, y, reinterpret_cast<T*>(l)); });
 }
 template <class T> int launch_big_trsv(const BigTrsvArgs<T>& a, void*)
 {
-    big_grid(a.B, 1, 64 * kTrsvNW, big_trsv_lds_elems(a.nb * kBB) * sizeof(T), [&](const Block& b, int qp, int, unsigned char* l) {
-        if (a.nb > 8) big_trsv_body<T, true>(b, a, qp, reinterpret_cast<T*>(l));
-        else big_trsv_body<T, false>(b, a, qp, reinterpret_cast<T*>(l));
+    return emu_per_qp<T>(a.B, 64 * kTrsvNW, big_trsv_lds_elems(a.nb * kBB) * sizeof(T), [&](const Block& b, int qp, T* lds) {
+        if (a.nb > 8) big_trsv_body<T, true>(b, a, qp, lds);
+        else big_trsv_body<T, false>(b, a, qp, lds);
     });
-    return QPX_OK;
 }
 template <class T> int launch_big_gemv(const BigGemvArgs<T>& a, void*)
 {
     const int outs = a.trans ? a.cols : a.rows;
-    big_grid(a.B, (outs + kBB - 1) / kBB, 256, big_gemv_lds_elems(a.trans ? a.rows : a.cols) * sizeof(T), [&](const Block& b, int qp, int y, unsigned char* l) { big_gemv_body<T>(b, a, qp, y, reinterpret_cast<T*>(l)); });
-    return QPX_OK;
+    return emu_grid(a.B, (outs + kBB - 1) / kBB, 256, big_gemv_lds_elems(a.trans ? a.rows : a.cols) * sizeof(T), [&](const Block& b, int qp, int y, unsigned char* l) { big_gemv_body<T>(b, a, qp, y, reinterpret_cast<T*>(l)); });
 }
 template <class T> int launch_big_symv(const BigSymvArgs<T>& a, void*)
 {
-    big_grid(a.B, a.stage == 0 ? a.ld / kBB : 1, 256, big_symv_lds_elems() * sizeof(T), [&](const Block& b, int qp, int y, unsigned char* l) { big_symv_body<T>(b, a, qp, y, reinterpret_cast<T*>(l)); });
-    return QPX_OK;
+    return emu_grid(a.B, a.stage == 0 ? a.ld / kBB : 1, 256, big_symv_lds_elems() * sizeof(T), [&](const Block& b, int qp, int y, unsigned char* l) { big_symv_body<T>(b, a, qp, y, reinterpret_cast<T*>(l)); });
 }
 template <class T> int launch_big_vec(const BigVecArgs<T>& a, void*)
 {
-    big_grid(a.B, 1, 256, 0, [&](const Block& b, int qp, int, unsigned char*) { big_vec_body<T>(b, a, qp); });
-    return QPX_OK;
+    return emu_grid(a.B, 1, 256, 0, [&](const Block& b, int qp, int, unsigned char*) { big_vec_body<T>(b, a, qp); });
 }
 template <class T> int launch_big_kkt(const BigKktArgs<T>& a, int gy, void*)
 {
-    big_grid(a.B, gy, 256, 0, [&](const Block& b, int qp, int y, unsigned char*) { big_kkt_body<T>(b, a, qp, y); });
-    return QPX_OK;
+    return emu_grid(a.B, gy, 256, 0, [&](const Block& b, int qp, int y, unsigned char*) { big_kkt_body<T>(b, a, qp, y); });
 }
 template <class T> int launch_big_phase(const BigPhaseArgs<T>& a, void*)
 {
-    const int ns = big_pad(a.m) / kWave;
-    big_grid(a.B, 1, 64, 0, [&](const Block& b, int qp, int, unsigned char*) {
-        if (ns == 1) big_phase_body<T, 1>(b, a, qp);
-        else if (ns == 2) big_phase_body<T, 2>(b, a, qp);
-        else if (ns <= 4) big_phase_body<T, 4>(b, a, qp);
-        else if (ns <= 8) big_phase_body<T, 8>(b, a, qp);
-        else big_phase_body<T, 16>(b, a, qp);
+    return big_ns_form(big_pad(a.m) / kWave, [&](auto ns) {
+        return emu_grid(a.B, 1, 64, 0, [&](const Block& b, int qp, int, unsigned char*) { big_phase_body<T, decltype(ns)::value>(b, a, qp); });
     });
-    return QPX_OK;
 }
-
 template <class T> int launch_big_solve(const BigSolveArgs<T>& a, void*)
 {
-    const int ns = big_pad(a.ph.m) / kWave;
-    big_grid(a.t.B, 1, 64 * kTrsvNW, big_trsv_lds_elems(a.t.nb * kBB) * sizeof(T), [&](const Block& b, int qp, int, unsigned char* l) {
-        T* lds = reinterpret_cast<T*>(l);
-        if (ns == 1) big_solve_body<T, 1>(b, a, qp, lds);
-        else if (ns == 2) big_solve_body<T, 2>(b, a, qp, lds);
-        else if (ns <= 4) big_solve_body<T, 4>(b, a, qp, lds);
-        else if (ns <= 8) big_solve_body<T, 8>(b, a, qp, lds);
-        else big_solve_body<T, 16>(b, a, qp, lds);
+    return big_ns_form(big_pad(a.ph.m) / kWave, [&](auto ns) {
+        return emu_per_qp<T>(a.t.B, 64 * kTrsvNW, big_trsv_lds_elems(a.t.nb * kBB) * sizeof(T), [&](const Block& b, int qp, T* lds) { big_solve_body<T, decltype(ns)::value>(b, a, qp, lds); });
     });
-    return QPX_OK;
 }
 template <class T> int launch_big_polish(const BigPolishArgs<T>& a, void*)
 {
     const BigLayout L = big_layout(a.n, a.m, a.q);
-    big_grid(a.B, 1, 64 * kBigPolWaves, big_polish_lds_doubles(L.VP) * sizeof(double), [&](const Block& b, int qp, int, unsigned char* l) {
-        big_polish_body<T>(b, a, qp, reinterpret_cast<double*>(l));
-    });
-    return QPX_OK;
+    return emu_per_qp<double>(a.B, 64 * kBigPolWaves, big_polish_lds_doubles(L.VP) * sizeof(double), [&](const Block& b, int qp, double* lds) { big_polish_body<T>(b, a, qp, lds); });
 }
 template <class T> int launch_big_diag(const BigDiagArgs<T>& a, void*)
 {
-    const int ns = big_pad(a.ph.m) / kWave;
-    big_grid(a.p.B, 1, 256, big_panel_lds_elems() * sizeof(T), [&](const Block& b, int qp, int, unsigned char* l) {
-        T* lds = reinterpret_cast<T*>(l);
-        if (ns == 1) big_diag_body<T, 1>(b, a, qp, lds);
-        else if (ns == 2) big_diag_body<T, 2>(b, a, qp, lds);
-        else if (ns <= 4) big_diag_body<T, 4>(b, a, qp, lds);
-        else if (ns <= 8) big_diag_body<T, 8>(b, a, qp, lds);
-        else big_diag_body<T, 16>(b, a, qp, lds);
+    return big_ns_form(big_pad(a.ph.m) / kWave, [&](auto ns) {
+        return emu_per_qp<T>(a.p.B, 256, big_panel_lds_elems() * sizeof(T), [&](const Block& b, int qp, T* lds) { big_diag_body<T, decltype(ns)::value>(b, a, qp, lds); });
     });
-    return QPX_OK;
 }
 
 template <class T> int launch_batch_outer(const OuterArgs<T>& a, int tiles, void*)
