@@ -13,7 +13,8 @@
  *   qpx_factor_solve_kkt .. qpth/solvers/pdipm/batch.py:435-470 + 349-372
  *                                                                  factor_kkt(S_LU,R,d); solve_kkt(...)
  *   qpx_backward .......... qpth/qp.py:127-182                     QPFunctionFn.backward (per-QP grads)
- *   qpx_jvp ............... (no reference counterpart)            QPFunctionFn.jvp: forward mode, the adjoint of qpx_backward
+ *   qpx_backward_duals .... (no reference counterpart)            the same for a loss of (zhat, lam, nu): cotangents on the multipliers
+ *   qpx_jvp ............... (no reference counterpart)            QPFunctionFn.jvp: forward mode, the adjoint of qpx_backward(_duals)
  *
  * Conventions
  *   - dtype: QPX_F32 or QPX_F64: every `void*` array below has that element type; or QPX_F32_WIDE (see the enum).
@@ -198,6 +199,25 @@ int qpx_backward(int dtype, int B, int n, int m, int q, void* factors, int64_t s
                  void* dx, void* dz, void* dy,
                  int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
                  int32_t* status, qpx_stream_t stream);
+
+/* Additive after v8 (QPX_ABI_VERSION stays 8): qpx_backward for a loss l(zhat, lam, nu) that also depends on the MULTIPLIERS
+ * -- qpx_backward's arguments plus the cotangents dl_dlam (B,m) and dl_dnu (B,q) of lam and nu, of dtype like dl_dz (float32
+ * under QPX_F32_WIDE).  The same launch with the right-hand side (rx, rs, rz, ry) = (dl_dz, 0, dl_dlam, dl_dnu) in the solver's
+ * convention K sol = -r, and the same six gradient formulas on the new (dx, dz, dy):
+ *   dQ = 1/2 (dx zhat' + zhat dx'), dp = dx, dG = dz zhat' + lam dx', dh = -dz, dA = dy zhat' + nu dx', db = -dy.
+ * Each of the three cotangents may be NULL = zero (dl_dnu is ignored when q = 0), but not all of them: QPX_ERR_ARG.  Exactly
+ * the adjoint of qpx_jvp's (dzhat, dlam, dnu):
+ *   <dl_dz, dzhat> + <dl_dlam, dlam> + <dl_dnu, dnu> = <dQ, tQ> + <dp, tp> + <dG, tG> + <dh, th> + <dA, tA> + <db, tb>  per QP.
+ * There is no cotangent of the slacks (rs stays zero: ds = (-rs - dz) / d with d from 1e-10 to 1e8 loses eight digits;
+ * DESIGN 4.5) -- a caller differentiates h - G zhat instead.  qpx_backward IS this call with dl_dlam = dl_dnu = NULL (and
+ * dl_dz required); everything else -- outputs, refine, Q, G, A, status -- as for qpx_backward. */
+int qpx_backward_duals(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac,
+                       const void* zhat, const void* lam, const void* slack, const void* nu,
+                       const void* dl_dz, const void* dl_dlam, const void* dl_dnu,
+                       void* dQ, void* dp, void* dG, void* dh, void* dA, void* db,
+                       void* dx, void* dz, void* dy,
+                       int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
+                       int32_t* status, qpx_stream_t stream);
 
 /* Additive after v8 (QPX_ABI_VERSION stays 8): FORWARD MODE of QPFunction -- the tangent of the solution at the given
  * (zhat, lam, slack, nu) along tangents tQ (B,n,n), tp (B,n), tG (B,m,n), th (B,m), tA (B,q,n), tb (B,q) of the six

@@ -46,6 +46,8 @@ _SIGNATURES = {
                                   _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "qpx_backward": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                           _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "qpx_backward_duals": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "qpx_jvp": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                      _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "qpx_polish_supported": (_i, [_i, _i, _i, _i]),
@@ -170,9 +172,18 @@ class QpxLib:
 
     # -- qp.py:127-182 --------------------------------------------------------------------
     def backward(self, B, n, m, q, factors, sfac, zhat, lam, slack, nu, dl_dz, dQ, dp, dG, dh, dA, db, status,
-                 dx=None, dz=None, dy=None, refine=0, Q=None, G=None, A=None, wide=False):
-        """Any of dQ..db may be None (gradient not wanted); dx, dz, dy: optional KKT solution outputs."""
+                 dx=None, dz=None, dy=None, refine=0, Q=None, G=None, A=None, wide=False, dl_dlam=None, dl_dnu=None):
+        """Any of dQ..db may be None (gradient not wanted); dx, dz, dy: optional KKT solution outputs.
+        dl_dlam (B,m), dl_dnu (B,q): cotangents of the multipliers (qpx_backward_duals; dl_dz may then be None).  Without
+        them the call is qpx_backward itself, as before."""
         Qp, Gp, Ap = Param(Q, 3), Param(G, 3), Param(A, 3)
+        if dl_dlam is not None or dl_dnu is not None or dl_dz is None:
+            self.check(self.dll.qpx_backward_duals(
+                _code(factors, wide), B, n, m, q, _ptr(factors), int(sfac), _ptr(zhat), _ptr(lam), _ptr(slack),
+                _ptr(nu), _ptr(dl_dz), _ptr(dl_dlam), _ptr(dl_dnu), _ptr(dQ), _ptr(dp), _ptr(dG), _ptr(dh), _ptr(dA), _ptr(db),
+                _ptr(dx), _ptr(dz), _ptr(dy), int(refine), Qp.ptr, Qp.stride, Gp.ptr, Gp.stride, Ap.ptr, Ap.stride,
+                _ptr(status), _stream(factors)))
+            return
         self.check(self.dll.qpx_backward(
             _code(factors, wide), B, n, m, q, _ptr(factors), int(sfac), _ptr(zhat), _ptr(lam), _ptr(slack),
             _ptr(nu), _ptr(dl_dz), _ptr(dQ), _ptr(dp), _ptr(dG), _ptr(dh), _ptr(dA), _ptr(db),

@@ -255,7 +255,7 @@ int api_kkt(KktArgs<T>& a, void* stream)
             s.d = advio(a.d, o * m, w); s.rx = advio(a.rx, o * n, w); s.rs = advio(a.rs, o * m, w); s.rz = advio(a.rz, o * m, w); s.ry = advio(a.ry, o * q, w);
             s.dx = advio(a.dx, o * n, w); s.ds = advio(a.ds, o * m, w); s.dz = advio(a.dz, o * m, w); s.dy = advio(a.dy, o * q, w);
             s.zhat = advio(a.zhat, o * n, w); s.lam = advio(a.lam, o * m, w); s.slack = advio(a.slack, o * m, w); s.nu = advio(a.nu, o * q, w);
-            s.dl_dz = advio(a.dl_dz, o * n, w);
+            s.dl_dz = advio(a.dl_dz, o * n, w); s.dl_dlam = advio(a.dl_dlam, o * m, w); s.dl_dnu = advio(a.dl_dnu, o * q, w);
             s.dQ = advio(a.dQ, o * n * n, w); s.dp = advio(a.dp, o * n, w); s.dG = advio(a.dG, o * m * n, w); s.dh = advio(a.dh, o * m, w);
             s.dA = advio(a.dA, o * q * n, w); s.db = advio(a.db, o * q, w);
             s.tQ = advio(a.tQ, o * a.stQ, w); s.tp = advio(a.tp, o * a.stp, w); s.tG = advio(a.tG, o * a.stG, w);
@@ -303,14 +303,15 @@ int api_factor_solve_kkt(int io32, int B, int n, int m, int q, void* factors, in
 
 template <class T>
 int api_backward(int io32, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat, const void* lam,
-                 const void* slack, const void* nu, const void* dl_dz, void* dQ, void* dp, void* dG, void* dh, void* dA, void* db,
-                 void* dx, void* dz, void* dy, int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A,
+                 const void* slack, const void* nu, const void* dl_dz, const void* dl_dlam, const void* dl_dnu, void* dQ, void* dp,
+                 void* dG, void* dh, void* dA, void* db, void* dx, void* dz, void* dy, int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A,
                  int64_t sA, int32_t* status, void* stream)
 {
     KktArgs<T> a{};
     a.io32 = io32;
     a.B = B; a.n = n; a.m = m; a.q = q; a.fac = (T*)factors; a.fac_stride = (size_t)sfac;
     a.zhat = (const T*)zhat; a.lam = (const T*)lam; a.slack = (const T*)slack; a.nu = (const T*)nu; a.dl_dz = (const T*)dl_dz;
+    a.dl_dlam = (const T*)dl_dlam; a.dl_dnu = q > 0 ? (const T*)dl_dnu : nullptr;
     a.dQ = (T*)dQ; a.dp = (T*)dp; a.dG = (T*)dG; a.dh = (T*)dh; a.dA = (T*)dA; a.db = (T*)db; a.status = status;
     a.dx = (T*)dx; a.dz = (T*)dz; a.dy = (T*)dy;
     a.refine = refine; a.Q = (const T*)Q; a.G = (const T*)G; a.A = (const T*)A; a.sQ = sQ; a.sG = sG; a.sA = sA;
@@ -557,16 +558,31 @@ int qpx_backward(int dtype, int B, int n, int m, int q, void* factors, int64_t s
                  int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
                  int32_t* status, qpx_stream_t stream)
 {
+    // (dl_dz is required here; checked behind the sizes, as it always was)
     const int e = qpx::check_dims(dtype, B, n, m, q);
     if (e) return e;
-    if (!factors || !zhat || !lam || !slack || !dl_dz || (q > 0 && !nu)) return QPX_ERR_ARG;
+    if (!dl_dz) return QPX_ERR_ARG;
+    return qpx_backward_duals(dtype, B, n, m, q, factors, sfac, zhat, lam, slack, nu, dl_dz, nullptr, nullptr, dQ, dp, dG, dh, dA, db,
+                              dx, dz, dy, refine, Q, sQ, G, sG, A, sA, status, stream);
+}
+
+int qpx_backward_duals(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat,
+                       const void* lam, const void* slack, const void* nu, const void* dl_dz, const void* dl_dlam,
+                       const void* dl_dnu, void* dQ, void* dp, void* dG, void* dh, void* dA, void* db, void* dx, void* dz,
+                       void* dy, int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
+                       int32_t* status, qpx_stream_t stream)
+{
+    const int e = qpx::check_dims(dtype, B, n, m, q);
+    if (e) return e;
+    if (!factors || !zhat || !lam || !slack || (q > 0 && !nu)) return QPX_ERR_ARG;
+    if (!dl_dz && !dl_dlam && !(q > 0 && dl_dnu)) return QPX_ERR_ARG;       // no cotangent at all
     if (refine < 0) return QPX_ERR_ARG;
     if (refine > 0 && !qpx_refine_supported(dtype, n, m, q)) return QPX_ERR_UNSUPPORTED;
     if (dtype != QPX_F32)
-        return qpx::api_backward<double>(dtype == QPX_F32_WIDE, B, n, m, q, factors, sfac, zhat, lam, slack, nu, dl_dz, dQ, dp, dG, dh, dA, db,
-                                         dx, dz, dy, refine, Q, sQ, G, sG, A, sA, status, stream);
-    return qpx::api_backward<float>(0, B, n, m, q, factors, sfac, zhat, lam, slack, nu, dl_dz, dQ, dp, dG, dh, dA, db, dx, dz, dy, refine,
-                                    Q, sQ, G, sG, A, sA, status, stream);
+        return qpx::api_backward<double>(dtype == QPX_F32_WIDE, B, n, m, q, factors, sfac, zhat, lam, slack, nu, dl_dz, dl_dlam, dl_dnu,
+                                         dQ, dp, dG, dh, dA, db, dx, dz, dy, refine, Q, sQ, G, sG, A, sA, status, stream);
+    return qpx::api_backward<float>(0, B, n, m, q, factors, sfac, zhat, lam, slack, nu, dl_dz, dl_dlam, dl_dnu, dQ, dp, dG, dh, dA, db,
+                                    dx, dz, dy, refine, Q, sQ, G, sG, A, sA, status, stream);
 }
 
 int qpx_jvp(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat, const void* lam,

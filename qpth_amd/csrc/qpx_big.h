@@ -1232,7 +1232,7 @@ template <class T> QPX_DEV void big_vec_body(const Block& b, const BigVecArgs<T>
 
 // KKT solve / backward set-up and epilogue on the blob's vectors (one workgroup per QP)
 //   stage 0: vD = 1/d (d given, or clamp(lam)/clamp(slack) for backward), vRH <- rs/d - rz, vU <- rx (n, padded 0),
-//            vBQ <- ry (q; backward: 0)
+//            vBQ <- ry (q); backward: rz = dl_dlam, ry = dl_dnu (NULL = 0: qpx_backward itself), rs = 0
 //   stage 1: outputs: dz = vX, ds = (-rs - dz)/d, dx = vW, dy = vNU; backward: dp, dh, db and the outer products
 template <class T> struct BigKktArgs {
     int B, n, m, stage, backward;
@@ -1248,6 +1248,8 @@ template <class T> struct BigKktArgs {
     int jvp = 0;
     const T *tp = nullptr, *th = nullptr, *tb = nullptr;
     long long stp = 0, sth = 0, stb = 0;
+    // backward with cotangents on the multipliers (qpx_backward_duals), stage 0: vRH = -dl_dlam, vBQ = dl_dnu; NULL = zeros
+    const T *dl_dlam = nullptr, *dl_dnu = nullptr;
 };
 template <class T> QPX_DEV void big_kkt_body(const Block& b, const BigKktArgs<T>& a, int qp, int chunk)
 {
@@ -1283,8 +1285,8 @@ template <class T> QPX_DEV void big_kkt_body(const Block& b, const BigKktArgs<T>
         return;
     }
     if (a.stage == 0) {
-        const In<T> rxg(a.backward ? a.dl_dz : a.rx, (size_t)qp * n, io32), rzg(a.backward ? nullptr : a.rz, (size_t)qp * m, io32);
-        const In<T> ryg((!a.backward && q > 0) ? a.ry : nullptr, (size_t)qp * q, io32), dg(a.backward ? nullptr : a.d, (size_t)qp * m, io32);
+        const In<T> rxg(a.backward ? a.dl_dz : a.rx, (size_t)qp * n, io32), rzg(a.backward ? a.dl_dlam : a.rz, (size_t)qp * m, io32);
+        const In<T> ryg(q > 0 ? (a.backward ? a.dl_dnu : a.ry) : nullptr, (size_t)qp * q, io32), dg(a.backward ? nullptr : a.d, (size_t)qp * m, io32);
         const In<T> lamg(a.backward ? a.lam : nullptr, (size_t)qp * m, io32), slg(a.backward ? a.slack : nullptr, (size_t)qp * m, io32);
         for (int i = b.tid; i < L.VP; i += b.nt) {
             T dinv = T(1), rhs = T(0);

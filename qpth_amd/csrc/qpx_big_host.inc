@@ -406,8 +406,8 @@ int big_ipm(const IpmArgs<T>& a, void* stream, int part = 0, int nparts = 1)
 // stage): vD = 1/d, vRH = rs/d - rz, vU = rx, vBQ = ry  ->  dz = vX, dx = vW, dy = vNU.
 //   u = Lq^-1 rx;  rhs += Ztp u + Vh L11^-1 ry;  T = R + 1/d;  dz = -T^-1 rhs;
 //   t = S11^-1 (ry - Yt u);  dx = -Lq^-T (u + Ztp^T dz + Yt^T t);  dy = t - L11^-T Vh^T dz
-// backward: ry = 0 (no L11^-1 ry term); factor = false: T's factor of the previous call is still in the blob (a second
-// right-hand side with the same d: the finishing stage's corrector)
+// backward (= "ry is zero": a backward without a cotangent on nu): no L11^-1 ry term; factor = false: T's factor of the
+// previous call is still in the blob (a second right-hand side with the same d: the finishing stage's corrector)
 template <class T>
 int big_kkt_core(const BigCtx<T>& c, bool backward, bool factor)
 {
@@ -474,6 +474,7 @@ int big_kkt(const KktArgs<T>& a, void* stream)
     BigKktArgs<T> k{};
     k.B = a.B; k.n = a.n; k.m = a.m; k.q = q; k.backward = kBw ? 1 : 0; k.fac = a.fac; k.fac_stride = a.fac_stride; k.io32 = a.io32;
     k.d = a.d; k.rx = a.rx; k.rs = a.rs; k.rz = a.rz; k.ry = a.ry; k.zhat = a.zhat; k.lam = a.lam; k.slack = a.slack; k.nu = a.nu; k.dl_dz = a.dl_dz;
+    k.dl_dlam = a.dl_dlam; k.dl_dnu = a.dl_dnu;
     k.dx = a.dx; k.ds = a.ds; k.dz = a.dz; k.dy = a.dy; k.dQ = a.dQ; k.dp = a.dp; k.dG = a.dG; k.dh = a.dh; k.dA = a.dA; k.db = a.db; k.status = a.status;
     if constexpr (!kBw) {
         k.jvp = a.jvp; k.tp = a.tp; k.th = a.th; k.tb = a.tb; k.stp = a.stp; k.sth = a.sth; k.stb = a.stb;
@@ -483,7 +484,8 @@ int big_kkt(const KktArgs<T>& a, void* stream)
     if constexpr (!kBw) {
         if (a.jvp && (e = big_jvp_products<T>(c, a))) return e;
     }
-    if ((e = big_kkt_core<T>(c, kBw, true))) return e;
+    // (a backward without a cotangent on nu has ry = 0: big_kkt_core leaves the L11^-1 ry term out, as it always did there)
+    if ((e = big_kkt_core<T>(c, kBw && !(q > 0 && a.dl_dnu), true))) return e;
     k.stage = 1;
     int rows = a.n > a.m ? a.n : a.m;
     return launch_big_kkt<T>(k, kBw ? 1 + (rows + 15) / 16 : 1, stream);

@@ -1438,12 +1438,17 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
     const int io32 = a.io32;
     const In<T> rxg(kBackward ? a.dl_dz : a.rx, (size_t)qp * n, io32);
     const In<T> rsg(kBackward ? nullptr : a.rs, (size_t)qp * m, io32);
-    const In<T> rzg(kBackward ? nullptr : a.rz, (size_t)qp * m, io32);
-    const In<T> ryg((!kBackward && q > 0) ? a.ry : nullptr, (size_t)qp * q, io32);
+    // (backward: the cotangents of lam and nu take the places of rz and ry -- NULL, i.e. zero, for qpx_backward itself)
+    const In<T> rzg(kBackward ? a.dl_dlam : a.rz, (size_t)qp * m, io32);
+    const In<T> ryg(q > 0 ? (kBackward ? a.dl_dnu : a.ry) : nullptr, (size_t)qp * q, io32);
     const In<T> lamg(kBackward ? a.lam : nullptr, (size_t)qp * m, io32), slg(kBackward ? a.slack : nullptr, (size_t)qp * m, io32);
     const In<T> dg(kBackward ? nullptr : a.d, (size_t)qp * m, io32);
     bool jvp = false;                                  // forward mode (qpx_jvp): never in the backward's instantiation
     if constexpr (!kBackward) jvp = a.jvp != 0;
+    // the backward with refinement keeps ry and rs/d - rz = -dl_dlam for the refinement's residuals where nu and lam will be
+    // staged for the outer products (vNU, vLM: free until then), as forward mode keeps its right-hand side -- the two
+    // cotangent pointers are dead before the factorisation, whose registers scalar spills would otherwise share
+    const bool stash = kBackward && a.refine > 0;
     QPX_PROF_INIT
 
     if (jvp) {
@@ -1473,7 +1478,10 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
         }
         vD[i] = dinv;
         vRH[i] = rhs;
+        if (stash) vLM[i] = rhs;
     }
+    if (stash)
+        for (int i = b.tid; i < q; i += NT) vNU[i] = ryg ? ryg[i] : T(0);
     Mat::sync(b);
     }
     // One application of the condensed KKT inverse: inputs rX (n), rY (q) and rH = rs/d - rz (M8),
@@ -1560,11 +1568,18 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
         const T* Gg = a.G + (size_t)qp * a.sG;
         const T* Ag = (q > 0 && a.A) ? a.A + (size_t)qp * a.sA : nullptr;
         for (int it = 0; it < a.refine; ++it) {
-            // (forward mode: rx, ry and rs/d - rz as formed from the tangents, kept in vZH, vNU, vLM; rs = 0 there)
-            for (int i = b.tid; i < n; i += NT) vRX[i] = jvp ? vZH[i] : (rxg ? rxg[i] : T(0));
-            for (int i = b.tid; i < q; i += NT) vRY[i] = jvp ? vNU[i] : (ryg ? ryg[i] : T(0));
-            for (int i = b.tid; i < M8; i += NT)     // -(ds + rz): the part of -resz that needs no matrix
-                vRH[i] = (i < m) ? (jvp ? vDZ[i] * vD[i] + vLM[i] : -((-(rsg ? rsg[i] : T(0)) - vDZ[i]) * vD[i] + (rzg ? rzg[i] : T(0)))) : T(0);
+            // (forward mode: rx, ry and rs/d - rz as formed from the tangents, kept in vZH, vNU, vLM; rs = 0 there.  The
+            // backward: ry and -rz kept in vNU, vLM -- zeros without cotangents on the multipliers, the values it always had)
+            const bool kept = jvp || kBackward;
+            // (backward: the thread's first index is laundered so that the LDS addresses of these three loops -- vNU and vLM
+            // among them -- are formed here, per step, and not kept in registers across the residual mat-vecs below, the
+            // register peak of the one-wave forms: 128 registers at two tile rows, the edge of four waves per SIMD)
+            int t0 = b.tid;
+            if constexpr (kBackward) QPX_LAUNDER_V(t0);
+            for (int i = t0; i < n; i += NT) vRX[i] = jvp ? vZH[i] : (rxg ? rxg[i] : T(0));
+            for (int i = t0; i < q; i += NT) vRY[i] = kept ? vNU[i] : ((!kBackward && ryg) ? ryg[i] : T(0));
+            for (int i = t0; i < M8; i += NT)     // -(ds + rz): the part of -resz that needs no matrix
+                vRH[i] = (i < m) ? (kept ? vDZ[i] * vD[i] + vLM[i] : -((-(rsg ? rsg[i] : T(0)) - vDZ[i]) * vD[i] + ((!kBackward && rzg) ? rzg[i] : T(0)))) : T(0);
             Mat::sync(b);
             // residuals accumulate in double whatever T is: fixed-precision refinement cannot improve the forward
             // error of an ill-conditioned solve (cond(Q) ~ 1e6 on the benchmark generator), mixed precision can

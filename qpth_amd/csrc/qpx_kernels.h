@@ -155,6 +155,9 @@ template <class T> struct KktArgs {
     int jvp = 0;
     const T *tQ = nullptr, *tp = nullptr, *tG = nullptr, *th = nullptr, *tA = nullptr, *tb = nullptr;   // NULL = zero
     long long stQ = 0, stp = 0, stG = 0, sth = 0, stA = 0, stb = 0;        // batch strides in elements (0 = shared)
+    // backward with cotangents on the multipliers (qpx_backward_duals): rz = dl_dlam (B,m), ry = dl_dnu (B,q) beside
+    // rx = dl_dz; NULL = zeros (and then dl_dz may be NULL too); rs stays zero
+    const T *dl_dlam = nullptr, *dl_dnu = nullptr;
 };
 
 // The finishing stage (qpx_polish, include/qpx.h): iterations of the reference's loop in the ORIGINAL variables

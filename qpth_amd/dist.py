@@ -86,13 +86,19 @@ def reduce_shared_grad(local_mean_grad, n_local, nBatch, group=None):
 
 def solve_sharded(qp_function, Q, p, G, h, A, b, nBatch, gather=True, group=None):
     """Solve the global batch data-parallel: this rank's slice through `qp_function`
-    (a QPFunction(...) callable); returns the local zhat and, if gather, the full one."""
+    (a QPFunction(...) callable); returns the local zhat and, if gather, the full one.  A callable that returns a tuple
+    (QPFunction(duals=True): zhat, nu, lam, slacks) comes back as the local tuple and, if gather, a tuple of the same
+    length with every output gathered to the full batch (values only, as for zhat) and None in the place of an empty one
+    (nu without equality constraints)."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     check_shardable([Q, p, G, h, A, b], nBatch, world)
     lQ, lp, lG, lh, lA, lb = shard_params([Q, p, G, h, A, b], nBatch, rank, world)
     z_local = qp_function(lQ, lp, lG, lh, lA, lb)
     if not gather:
         return z_local, None
+    if isinstance(z_local, tuple):
+        # (decided by the outputs' shapes, which are the same on every rank: no rank skips a collective)
+        return z_local, tuple(gather_batch(v.detach(), nBatch, group) if v.shape[1:].numel() > 0 else None for v in z_local)
     return z_local, gather_batch(z_local.detach(), nBatch, group)
 
 

@@ -358,11 +358,15 @@ a non-zero diagonal.
         return (dz, dl, dn) if want_duals else dz
 
     # -- QPFunctionFn.backward (qp.py:127-182) ------------------------------------------------
-    def backward(self, zhat, lam, slacks, nu, dl_dz, want=(True,) * 6, shared=(False,) * 6, refine=0):
+    def backward(self, zhat, lam, slacks, nu, dl_dz, want=(True,) * 6, shared=(False,) * 6, refine=0,
+                 dl_dlam=None, dl_dnu=None):
         """Gradients (dQ, dp, dG, dh, dA, db) for the parameters `want` asks for (ctx.needs_input_grad;
         the others come back as None and cost nothing).  A parameter flagged in `shared` is one the whole
         batch shares: its gradient is returned already reduced to the reference's `.mean(0)` (qp.py:159-177)
-        -- for the matrices by one contraction over the batch (qpx_batch_outer) instead of B outer products."""
+        -- for the matrices by one contraction over the batch (qpx_batch_outer) instead of B outer products.
+        dl_dlam (B, m), dl_dnu (B, q): cotangents of the multipliers lam*, nu* (None = zero; dl_dz may then be None too,
+        but not all three): the same launch with the right-hand side (dl_dz, 0, dl_dlam, dl_dnu) -- qpx_backward_duals,
+        the exact adjoint of jvp(..., want_duals=True)."""
         B, n, m, q = self.B, self.n, self.m, self.q
         dt, dev = self.dtype, self.device
         wQ, wp, wG, wh, wA, wb = [bool(w) for w in want]
@@ -386,10 +390,14 @@ a non-zero diagonal.
         dz = buf((wh and sh) or (wG and sG), B, m)
         dy = buf(q > 0 and ((wb and sb) or (wA and sA)), B, q)
         zh, lm, nv = self._vec(zhat, n, "zhat"), self._vec(lam, m, "lam"), self._vec(nu, q, "nu")
+        gz, gl, gn = self._vec(dl_dz, n, "dl_dz"), self._vec(dl_dlam, m, "dl_dlam"), self._vec(dl_dnu, q, "dl_dnu")
+        if gz is None and gl is None and gn is None:
+            raise RuntimeError("qpth_amd: backward needs at least one of dl_dz, dl_dlam, dl_dnu")
+        duals = {} if (gl is None and gn is None and gz is not None) else {"dl_dlam": gl, "dl_dnu": gn}
         with self._knob():
             self.lib.backward(B, n, m, q, self.blob, self.sfac, zh, lm, self._vec(slacks, m, "slacks"), nv,
-                              self._vec(dl_dz, n, "dl_dz"), dQ, dp, dG, dh, dA, db, self.status, dx, dz, dy,
-                              refine=refine, Q=self.Q, G=self.G, A=self.A, wide=self.wide)
+                              gz, dQ, dp, dG, dh, dA, db, self.status, dx, dz, dy,
+                              refine=refine, Q=self.Q, G=self.G, A=self.A, wide=self.wide, **duals)
         with self._knob():           # (their launches too need the factors' device current)
             if wQ and sQ:
                 dQ = torch.empty(n, n, dtype=dt, device=dev)

@@ -10,6 +10,7 @@ means "no such constraint" (qp.py:58-61).  The forward runs two HIP kernels
 products); state crosses from forward to backward on ctx exactly as in the reference.
 Forward mode (torch.autograd.forward_ad, which the reference does not support) is one more launch: QPFunctionFn.jvp solves
 the backward's KKT system with the right-hand side formed from the input tangents (qpx_jvp).
+QPFunction(duals=True) also returns the multipliers, differentiable in both modes: (zhat, nu, lam, slacks).
 """
 from enum import Enum
 
@@ -50,8 +51,16 @@ def f64_arithmetic_serves(nz, nineq, neq, lib=None):
 
 def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                maxIter=20, solver=QPSolvers.PDIPM_BATCHED,
-               check_Q_spd=True, refine=None):
-    """`refine` is the one argument the reference does not have.  For float32 inputs:
+               check_Q_spd=True, refine=None, duals=False):
+    """`refine` and `duals` are the arguments the reference does not have.
+    duals=True: the call returns (zhat, nu, lam, slacks) -- the reference forward's order (batch.py:47-207) -- instead of
+      zhat alone.  zhat, lam (nBatch, nineq) and nu (nBatch, neq) are differentiable in all six parameters, in reverse and in
+      forward mode: a loss l(zhat, lam, nu) back-propagates through the same single backward launch, its KKT right-hand side
+      (dl/dzhat, 0, dl/dlam, dl/dnu) (qpx_backward_duals).  slacks is returned NON-differentiable (a cotangent on
+      it is numerically poor in this formulation, DESIGN 4.5: write h - G zhat where gradients through the slacks are
+      needed); without equality constraints nu is an empty (nBatch, 0) tensor, non-differentiable too.  An output the loss
+      does not use costs nothing: its cotangent reaches the kernel as NULL, not as zeros.
+    `refine`, for float32 inputs:
       None (automatic) -- sizes the float64 tile kernels serve (f64_arithmetic_serves): the float64 kernels run on the
             float32 tensors (they widen on load and narrow results and gradients on store; the factors between
             forward and backward are float64); other sizes: as refine=2;
@@ -117,7 +126,18 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             # output's grad_fn), and on the external-solver path the matrices the factors are rebuilt from
             ctx.zhat = zhats.detach()
             ctx.QGA = (Q.detach(), G.detach(), A.detach(), nBatch) if ctx.fac is None else None
-            return zhats
+            if not duals:
+                return zhats
+            # the multipliers as outputs: ctx keeps detached aliases (no cycle through the outputs' grad_fn), and an output
+            # the loss does not use hands backward None instead of a tensor of zeros
+            nus, lams, slacks = ctx.nus, ctx.lams, ctx.slacks
+            ctx.nus, ctx.lams, ctx.slacks = nus.detach(), lams.detach(), slacks.detach()
+            ctx.set_materialize_grads(False)
+            if neq == 0:
+                ctx.mark_non_differentiable(slacks, nus)
+            else:
+                ctx.mark_non_differentiable(slacks)
+            return zhats, nus, lams, slacks
 
         @staticmethod
         def jvp(ctx, dQ, dp, dG, dh, dA, db):
@@ -128,11 +148,15 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                 Q, G, A, nBatch = ctx.QGA
                 fac = KKTFactors.build(Q, G, A, nBatch)
                 fac.raise_on_failure(check_Q_spd)
-            return fac.jvp(ctx.zhat, ctx.lams, ctx.slacks, ctx.nus, (dQ, dp, dG, dh, dA, db),
-                           refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0)
+            rf = 1 if (ctx.refine > 0 and fac.refine_ok) else 0
+            if not duals:
+                return fac.jvp(ctx.zhat, ctx.lams, ctx.slacks, ctx.nus, (dQ, dp, dG, dh, dA, db), refine=rf)
+            # (z', nu', lam') from the same single launch; the slacks carry no tangent (non-differentiable)
+            zt, lt, nt = fac.jvp(ctx.zhat, ctx.lams, ctx.slacks, ctx.nus, (dQ, dp, dG, dh, dA, db), refine=rf, want_duals=True)
+            return zt, nt, lt, None
 
         @staticmethod
-        def backward(ctx, dl_dzhat):
+        def backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
             zhats, Q, p, G, h, A, b = ctx.saved_tensors
             nBatch = extract_nBatch(Q, p, G, h, A, b)
             Q, Q_e = expandParam(Q, nBatch, 3)
@@ -142,13 +166,16 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             A, A_e = expandParam(A, nBatch, 3)
             b, b_e = expandParam(b, nBatch, 2)
             neq = ctx.neq
+            if dl_dzhat is None and dl_dlam is None and (dl_dnu is None or neq == 0):
+                return (None,) * 6                                   # duals=True and no cotangent on any differentiable output
 
             fac = ctx.fac
             if fac is None:                                          # qp.py:142-143
                 fac = KKTFactors.build(Q, G, A, nBatch)
                 fac.raise_on_failure(check_Q_spd)
 
-            # d = clamp(lams)/clamp(slacks), factor_kkt, solve_kkt(dl_dzhat, 0, 0, 0) and the outer
+            # d = clamp(lams)/clamp(slacks), factor_kkt, solve_kkt(dl_dzhat, 0, 0, 0) -- with duals=True
+            # solve_kkt(dl_dzhat, 0, dl_dlam, dl_dnu), each None where the loss does not use that output -- and the outer
             # products (qp.py:148-173) happen inside one kernel.  Only the gradients autograd asks for are
             # formed (ctx.needs_input_grad), and the `.mean(0)` of a parameter the batch shares
             # (qp.py:159-177) is taken inside KKTFactors.backward -- for Q, G, A as one contraction over
@@ -156,7 +183,8 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             want = tuple(ctx.needs_input_grad[:6])
             grads = fac.backward(zhats, ctx.lams, ctx.slacks, ctx.nus, dl_dzhat, want=want,
                                  shared=(Q_e, p_e, G_e, h_e, A_e, b_e),
-                                 refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0)
+                                 refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0,
+                                 dl_dlam=dl_dlam, dl_dnu=dl_dnu if neq > 0 else None)
             if neq == 0:
                 grads = grads[:4] + (None, None)
             return grads
