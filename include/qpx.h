@@ -15,6 +15,7 @@
  *   qpx_backward .......... qpth/qp.py:127-182                     QPFunctionFn.backward (per-QP grads)
  *   qpx_backward_duals .... (no reference counterpart)            the same for a loss of (zhat, lam, nu): cotangents on the multipliers
  *   qpx_jvp ............... (no reference counterpart)            QPFunctionFn.jvp: forward mode, the adjoint of qpx_backward(_duals)
+ *   qpx_factor_solve_kkt_multi  (no reference counterpart)       factor_kkt once, solve_kkt for K right-hand sides per QP: Jacobians
  *
  * Conventions
  *   - dtype: QPX_F32 or QPX_F64: every `void*` array below has that element type; or QPX_F32_WIDE (see the enum).
@@ -236,6 +237,23 @@ int qpx_jvp(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac,
             void* dzhat, void* dlam, void* dnu, void* dslack,
             int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
             int32_t* status, qpx_stream_t stream);
+
+/* Additive after v8 (QPX_ABI_VERSION stays 8): qpx_factor_solve_kkt for K RIGHT-HAND SIDES per QP in one launch -- T = R + diag(1/d)
+ * is factored ONCE per QP (it depends on d alone), then the K solves run in blocks through the condensed inverse, each block
+ * streaming the blob's matrices once.  What K calls of qpx_backward / qpx_factor_solve_kkt at one solution cost K
+ * factorisations for: Jacobians of the solution, sensitivity analysis, per-sample gradients (qpth_amd/sensitivity.py).
+ * d (B,m) > 0, one per QP.  rx (B,K,n), rs, rz (B,K,m), ry (B,K,q): a QP's K vectors contiguous, row-major; NULL = zeros, but
+ * not all of them (ry is ignored when q = 0): QPX_ERR_ARG.  dx (B,K,n) required; ds, dz (B,K,m), dy (B,K,q): NULL = skip.
+ * K >= 1 is a run-time argument; K = 1 computes what qpx_factor_solve_kkt computes (refine = 0).  sfac = 0 (shared factors) as
+ * everywhere.  There is no refinement here.  Served where qpx_multi_supported returns 1 under the calling thread's knob: the
+ * thread-grid / tile kernels (nz+neq+nineq <= 208), dtype QPX_F32, QPX_F64 or QPX_F32_WIDE; the large-QP family returns
+ * QPX_ERR_UNSUPPORTED (call qpx_factor_solve_kkt K times there).  A breakdown of the factorisation ORs QPX_ST_KKT_BREAKDOWN
+ * into status and returns zeros for dz, as the single solve does. */
+int qpx_multi_supported(int dtype, int n, int m, int q);
+int qpx_factor_solve_kkt_multi(int dtype, int B, int n, int m, int q, int K, void* factors, int64_t sfac,
+                               const void* d, const void* rx, const void* rs, const void* rz, const void* ry,
+                               void* dx, void* ds, void* dz, void* dy,
+                               int32_t* status, qpx_stream_t stream);
 
 /* v6: the FINISHING STAGE as one kernel -- `steps` iterations of the reference's PDIPM loop in the original variables
  * (qpth/solvers/pdipm/batch.py:92-198: affine + centring-corrector Newton steps, step lengths batch.py:189-198) started

@@ -50,6 +50,8 @@ _SIGNATURES = {
                                 _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "qpx_jvp": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                      _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "qpx_multi_supported": (_i, [_i, _i, _i, _i]),
+    "qpx_factor_solve_kkt_multi": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qpx_polish_supported": (_i, [_i, _i, _i, _i]),
     "qpx_polish": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                         _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -169,6 +171,13 @@ class QpxLib:
             _code(factors, wide), B, n, m, q, _ptr(factors), int(sfac), _ptr(d), _ptr(rx), _ptr(rs), _ptr(rz),
             _ptr(ry), _ptr(dx), _ptr(ds), _ptr(dz), _ptr(dy), int(refine), Qp.ptr, Qp.stride, Gp.ptr, Gp.stride,
             Ap.ptr, Ap.stride, _ptr(status), _stream(factors)))
+
+    # -- factor_kkt once, solve_kkt for K right-hand sides per QP (no reference counterpart) ------
+    def factor_solve_kkt_multi(self, B, n, m, q, K, factors, sfac, d, rx, rs, rz, ry, dx, ds, dz, dy, status, wide=False):
+        """rx .. ry, dx .. dy: (B, K, .) contiguous or None (zeros / not wanted; dx required)"""
+        self.check(self.dll.qpx_factor_solve_kkt_multi(
+            _code(factors, wide), B, n, m, q, int(K), _ptr(factors), int(sfac), _ptr(d), _ptr(rx), _ptr(rs), _ptr(rz),
+            _ptr(ry), _ptr(dx), _ptr(ds), _ptr(dz), _ptr(dy), _ptr(status), _stream(factors)))
 
     # -- qp.py:127-182 --------------------------------------------------------------------
     def backward(self, B, n, m, q, factors, sfac, zhat, lam, slack, nu, dl_dz, dQ, dp, dG, dh, dA, db, status,

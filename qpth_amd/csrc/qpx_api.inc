@@ -236,12 +236,18 @@ int api_ipm(int B, int n, int m, int q, const void* p, int64_t sp, const void* h
     return QPX_ERR_UNSUPPORTED;
 }
 
-template <class T, bool kBw>
+// kRole: 0 the KKT solve, 1 the backward, 2 the solve for a.K right-hand sides per QP (qpx_forms.h: kKktMultiRole) -- the
+// third role of the form the first two run in, so all three follow one rule for which form serves a size
+template <class T, int kRole>
 int api_kkt(KktArgs<T>& a, void* stream)
 {
+    constexpr bool kBw = kRole == 1;
+    constexpr int kForm = kRole == 2 ? kKktMultiRole : 0;
     const int n = a.n, m = a.m, q = a.q;
     a.images = blob_images<T>(n, m, q);
-    if (a.images == 8) {
+    if constexpr (kRole == 2) {
+        if (a.images == 8) return QPX_ERR_UNSUPPORTED;       // the large-QP family has no such kernels: K calls of the single solve
+    } else if (a.images == 8) {
         if (a.fac_stride == 0 && a.B > 1) return QPX_ERR_ARG;
         // (parts only when the knob asks for them: one factorisation + one solve is too short a sequence for two parts to
         // fill each other's gaps -- same box, backward by events, one part / two: C4 0.643 / 0.645 ms, B=128 n=300 m=200 q=50
@@ -270,15 +276,15 @@ int api_kkt(KktArgs<T>& a, void* stream)
             if ((g_grid_size == 0 || g_grid_size == 1) && nbt > 0) {
                 const int nw = tile_waves(nbt, a.B);
                 const bool ch = tile_chain(nbt, nw);
-                const size_t tb = lds_elems_kkt_tile(nbt, nw, n, q, ch) * sizeof(T);
-#define QPX_PICK(NBL, NW, CH) if (nbt == NBL && nw == NW && ch == CH) return launch_kkt_tile<NBL, NW, kBw, CH>(a, tb, stream);
+                const size_t tb = (kRole == 2 ? lds_elems_kkt_multi_tile(nbt, nw, n, q, ch) : lds_elems_kkt_tile(nbt, nw, n, q, ch)) * sizeof(T);
+#define QPX_PICK(NBL, NW, CH) if (nbt == NBL && nw == NW && ch == CH) return launch_kkt_tile<kForm + NBL, NW, kBw, CH>(a, tb, stream);
                 QPX_FORMS_KKT_TILE(QPX_PICK)        // no such form: on to the 16x16 grid
 #undef QPX_PICK
             }
         }
         const int nbg = grid_nb(m);
-        const size_t gb = lds_elems_kkt_grid(16, nbg, n, q) * sizeof(T);
-#define QPX_PICK(NBL) if (nbg == NBL) return launch_kkt_grid<T, NBL, kBw>(a, gb, stream);
+        const size_t gb = (kRole == 2 ? lds_elems_kkt_multi_grid(16, nbg, n, q) : lds_elems_kkt_grid(16, nbg, n, q)) * sizeof(T);
+#define QPX_PICK(NBL) if (nbg == NBL) return launch_kkt_grid<T, kForm + NBL, kBw>(a, gb, stream);
         QPX_FORMS_KKT_GRID(QPX_PICK)
 #undef QPX_PICK
         return QPX_ERR_UNSUPPORTED;
@@ -298,7 +304,21 @@ int api_factor_solve_kkt(int io32, int B, int n, int m, int q, void* factors, in
     a.dx = (T*)dx; a.ds = (T*)ds; a.dz = (T*)dz; a.dy = (T*)dy;
     a.status = status;
     a.refine = refine; a.Q = (const T*)Q; a.G = (const T*)G; a.A = (const T*)A; a.sQ = sQ; a.sG = sG; a.sA = sA;
-    return api_kkt<T, false>(a, stream);
+    return api_kkt<T, 0>(a, stream);
+}
+
+template <class T>
+int api_factor_solve_kkt_multi(int io32, int B, int n, int m, int q, int K, void* factors, int64_t sfac, const void* d, const void* rx,
+                               const void* rs, const void* rz, const void* ry, void* dx, void* ds, void* dz, void* dy,
+                               int32_t* status, void* stream)
+{
+    KktArgs<T> a{};
+    a.io32 = io32;
+    a.B = B; a.n = n; a.m = m; a.q = q; a.K = K; a.fac = (T*)factors; a.fac_stride = (size_t)sfac;
+    a.d = (const T*)d; a.rx = (const T*)rx; a.rs = (const T*)rs; a.rz = (const T*)rz; a.ry = q > 0 ? (const T*)ry : nullptr;
+    a.dx = (T*)dx; a.ds = (T*)ds; a.dz = (T*)dz; a.dy = (T*)dy;
+    a.status = status;
+    return api_kkt<T, 2>(a, stream);
 }
 
 template <class T>
@@ -315,10 +335,10 @@ int api_backward(int io32, int B, int n, int m, int q, void* factors, int64_t sf
     a.dQ = (T*)dQ; a.dp = (T*)dp; a.dG = (T*)dG; a.dh = (T*)dh; a.dA = (T*)dA; a.db = (T*)db; a.status = status;
     a.dx = (T*)dx; a.dz = (T*)dz; a.dy = (T*)dy;
     a.refine = refine; a.Q = (const T*)Q; a.G = (const T*)G; a.A = (const T*)A; a.sQ = sQ; a.sG = sG; a.sA = sA;
-    return api_kkt<T, true>(a, stream);
+    return api_kkt<T, 1>(a, stream);
 }
 
-// forward mode: the KKT solve of the backward (same d, same kernels: api_kkt<T, false>) with the right-hand side formed from
+// forward mode: the KKT solve of the backward (same d, same kernels: api_kkt<T, 0>) with the right-hand side formed from
 // the tangents inside them (KktArgs::jvp)
 template <class T>
 int api_jvp(int io32, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat, const void* lam,
@@ -339,7 +359,7 @@ int api_jvp(int io32, int B, int n, int m, int q, void* factors, int64_t sfac, c
     a.dx = (T*)dzhat; a.dz = (T*)dlam; a.dy = (T*)dnu; a.ds = (T*)dslack;
     a.status = status;
     a.refine = refine; a.Q = (const T*)Q; a.G = (const T*)G; a.A = (const T*)A; a.sQ = sQ; a.sG = sG; a.sA = sA;
-    return api_kkt<T, false>(a, stream);
+    return api_kkt<T, 0>(a, stream);
 }
 
 // the finishing stage: every family has it (thread-grid / tile kernels: one kernel, the blob's register image of R decides the
@@ -550,6 +570,28 @@ int qpx_factor_solve_kkt(int dtype, int B, int n, int m, int q, void* factors, i
         return qpx::api_factor_solve_kkt<double>(dtype == QPX_F32_WIDE, B, n, m, q, factors, sfac, d, rx, rs, rz, ry, dx, ds, dz, dy, refine,
                                                  Q, sQ, G, sG, A, sA, status, stream);
     return qpx::api_factor_solve_kkt<float>(0, B, n, m, q, factors, sfac, d, rx, rs, rz, ry, dx, ds, dz, dy, refine, Q, sQ, G, sG, A, sA, status, stream);
+}
+
+int qpx_multi_supported(int dtype, int n, int m, int q)
+{
+    // the thread-grid / tile KKT kernels have the multi-right-hand-side role (qpx_grid.h: kkt_multi_role), in all three dtypes
+    if (qpx::check_dims(dtype, 1, n, m, q) != QPX_OK) return 0;
+    return qpx::use_grid(n, m, q) ? 1 : 0;
+}
+
+int qpx_factor_solve_kkt_multi(int dtype, int B, int n, int m, int q, int K, void* factors, int64_t sfac, const void* d,
+                               const void* rx, const void* rs, const void* rz, const void* ry, void* dx, void* ds, void* dz,
+                               void* dy, int32_t* status, qpx_stream_t stream)
+{
+    const int e = qpx::check_dims(dtype, B, n, m, q);
+    if (e) return e;
+    if (K < 1 || !factors || !d || !dx) return QPX_ERR_ARG;
+    if (!rx && !rs && !rz && !(q > 0 && ry)) return QPX_ERR_ARG;          // no right-hand side at all
+    if (!qpx_multi_supported(dtype, n, m, q)) return QPX_ERR_UNSUPPORTED;
+    if (dtype != QPX_F32)
+        return qpx::api_factor_solve_kkt_multi<double>(dtype == QPX_F32_WIDE, B, n, m, q, K, factors, sfac, d, rx, rs, rz, ry, dx, ds, dz,
+                                                       dy, status, stream);
+    return qpx::api_factor_solve_kkt_multi<float>(0, B, n, m, q, K, factors, sfac, d, rx, rs, rz, ry, dx, ds, dz, dy, status, stream);
 }
 
 int qpx_backward(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat,

@@ -19,6 +19,17 @@ template <class F> inline int big_ns_form(int ns, F&& f)
     return f(std::integral_constant<int, 16>{});
 }
 
+// Every KKT form exists in three roles: the solve, the backward (the launchers' kBw) and the solve for K right-hand sides
+// in one launch (qpx_factor_solve_kkt_multi; qpx_grid.h: kkt_multi_role).  The third travels in the form's FIRST parameter,
+// block / tile rows + kKktMultiRole: every launcher of the family -- the GPU's and the host-thread emulator's -- reaches it
+// through the template it already has (kkt_grid_body / kkt_tile_body decode it).
+constexpr int kKktMultiRole = 64;
+// Right-hand sides per block of that role, every form: the products keep a block's accumulators (4 rows x RB in the row dots)
+// beside the register-resident factor, and with eight every tile form but the seven-row chain-wave form and the larger
+// float64 thread-grid forms spilled (6 .. 89 registers); at seven tile rows eight would also be the LDS of the second
+// workgroup of a CU.  qpth_amd/kkt.py: MULTI_RHS_BLOCK.
+constexpr int kKktMultiRB = 4;
+
 }  // namespace qpx
 
 // thread-grid kernels: (blocks of 16 -- of 8 in the one-wave grid -- per side), (blocks, slots of 64 columns)
@@ -26,7 +37,7 @@ template <class F> inline int big_ns_form(int ns, F&& f)
 #define QPX_FORMS_IPM_GRID(X) \
     X(1, 1) X(1, 2) X(1, 4) X(2, 1) X(2, 2) X(2, 4) X(4, 1) X(4, 2) X(4, 4) X(7, 2) X(7, 4) X(10, 4) X(13, 4)
 #define QPX_FORMS_IPM_GRID8(X) X(2, 1) X(2, 2) X(4, 1) X(4, 2) X(8, 1) X(8, 2) X(13, 2)
-#define QPX_FORMS_KKT_GRID(X) X(1) X(2) X(4) X(7) X(10) X(13)                 // each as the KKT solve and as the backward
+#define QPX_FORMS_KKT_GRID(X) X(1) X(2) X(4) X(7) X(10) X(13)                 // each as the KKT solve, as the backward and as the multi-right-hand-side solve
 #define QPX_FORMS_POLISH_GRID(X) X(1) X(2) X(4) X(7) X(10) X(13)
 // matrix-core tile kernels, f64: (tile rows, waves per QP, [slots,] chain-wave form)
 #define QPX_FORMS_IPM_TILE(X)                                                                                    \
@@ -35,6 +46,6 @@ template <class F> inline int big_ns_form(int ns, F&& f)
     X(7, 2, 2, false) X(7, 2, 4, false)                                                                          \
     X(7, 4, 2, true) X(7, 4, 4, true) X(4, 4, 1, true) X(4, 4, 2, true) X(4, 4, 4, true)
 #define QPX_FORMS_KKT_TILE(X) \
-    X(1, 1, false) X(2, 1, false) X(4, 1, false) X(4, 2, false) X(7, 2, false) X(7, 4, true) X(4, 4, true)   // each as the KKT solve and as the backward
+    X(1, 1, false) X(2, 1, false) X(4, 1, false) X(4, 2, false) X(7, 2, false) X(7, 4, true) X(4, 4, true)   // each in the three roles, as above
 #define QPX_FORMS_POLISH_TILE(X) X(1, 1, false) X(2, 1, false) X(4, 1, false) X(4, 4, true) X(7, 4, true)
 #define QPX_FORMS_PREFAC_TILE(X) X(4, false) X(7, false) X(4, true) X(7, true)    // (tile rows of nz + neq, with equalities)

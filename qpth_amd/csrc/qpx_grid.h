@@ -20,6 +20,7 @@
 // IPM's matrices (z* error vs the reference 2.7e-12 max at C2 in f64; a full explicit T^-1 by
 // Gauss-Jordan would lose 7 digits) -- see DESIGN.md section 7.
 #pragma once
+#include "qpx_forms.h"
 #include "qpx_kernels.h"
 
 namespace qpx {
@@ -1406,6 +1407,33 @@ QPX_DEV void kkt_jvp_rhs(const Block& b, const KktArgs<T>& a, int qp, T* vD, T* 
 }
 
 // ------------------------------------------------------------------------------------------
+// factor_kkt (batch.py:435-470): T = R + diag(1/d) from the blob's register image of R, factored in place -- E: W~ = L~^-1,
+// rd = 1/d_k (ldl_inv).  vD: 1/d, 1 on the pad.  `loaded` runs between the load and the factorisation (the phase timers of
+// the profiling build).  false: a pivot broke down (uniform).  Shared by the KKT solve / backward (kkt_mat_role) and the
+// multi-right-hand-side solve (kkt_multi_role).
+template <class T, class Mat, class P, class Loaded>
+QPX_DEV bool kkt_factor(const Block& b, const P& g, typename Mat::Regs& E, const T* img, const T* vD, T* scr, T* rd, int m, Loaded&& loaded)
+{
+    if constexpr (Mat::kAhead) {
+        // (r6) chain-wave form: the chain wave eliminates pivot block 0 -- R(0,0) from its own five loads + 1/d -- while the
+        // tile waves fetch their 57 KB of R; one barrier in front of the panels instead of three (TileMat::kAhead)
+        typename Mat::Ahead ah;
+        Mat::ahead_init(b, g, ah, img);
+        Mat::load(b, g, E, img);
+        Mat::ahead_pivot0(b, g, ah, vD, scr, rd, m);
+        Mat::ahead_publish0(b, g, E, vD, scr);
+        Mat::sync(b);
+        loaded();
+        return Mat::ldl_inv_ahead(b, g, E, scr, rd, m, [] {}, [] {}, [] {}, [] { return 0; }) == 0;
+    } else {
+        Mat::load(b, g, E, img);
+        Mat::add_diag(g, E, vD);
+        loaded();
+        return Mat::ldl_inv(b, g, E, scr, rd, m);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // factor_kkt + solve_kkt for arbitrary right-hand sides and QPFunctionFn.backward on the
 // format-3 blob (see kkt_body for the reference citations):
 //   dz = -T^-1 (M rx + W ry + rs/d - rz),  dx = -K rx - M^T dz - N ry,
@@ -1511,24 +1539,7 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
     // round trip to HBM runs under theirs: 1.5 us SLOWER at C2, 0.0499 vs 0.0485 ms, same box -- the image's 57 KB then
     // compete with the 160 KB the products stream.  profiles/r05f_ab_symv_prefetch_and_backward_load_order.txt)
     typename Mat::Regs E;
-    bool ok;
-    if constexpr (Mat::kAhead) {
-        // (r6) chain-wave form: the chain wave eliminates pivot block 0 -- R(0,0) from its own five loads + 1/d -- while the
-        // tile waves fetch their 57 KB of R; one barrier in front of the panels instead of three (TileMat::kAhead)
-        typename Mat::Ahead ah;
-        Mat::ahead_init(b, g, ah, Mat::image(F, lay));
-        Mat::load(b, g, E, Mat::image(F, lay));
-        Mat::ahead_pivot0(b, g, ah, vD, scr, rd, m);
-        Mat::ahead_publish0(b, g, E, vD, scr);
-        Mat::sync(b);
-        QPX_PROF(2)
-        ok = Mat::ldl_inv_ahead(b, g, E, scr, rd, m, [] {}, [] {}, [] {}, [] { return 0; }) == 0;
-    } else {
-        Mat::load(b, g, E, Mat::image(F, lay));
-        Mat::add_diag(g, E, vD);
-        QPX_PROF(2)
-        ok = Mat::ldl_inv(b, g, E, scr, rd, m);
-    }
+    const bool ok = kkt_factor<T, Mat>(b, g, E, Mat::image(F, lay), vD, scr, rd, m, [&] { QPX_PROF(2) });
     QPX_PROF(3)
     if (!ok && b.tid == 0 && a.status) a.status[qp] |= QPX_ST_KKT_BREAKDOWN;
     auto finish = [&](const T* rX, const T* rY, T* rH, T* oZ, T* oX, T* oY) {
@@ -1665,10 +1676,256 @@ QPX_DEV void kkt_mat_body(const Block& b, const KktArgs<T>& a, int qp, T* lds)
     Mat::with_role(g, [&](const auto& gp) { kkt_mat_role<T, Mat, kBackward>(b, a, qp, lds, gp); });
 }
 
+// ------------------------------------------------------------------------------------------
+// K right-hand sides per QP in ONE launch (qpx_factor_solve_kkt_multi): T = R + diag(1/d) is loaded and factored once
+// (kkt_factor), then the right-hand sides go through the condensed inverse of kkt_mat_role in blocks of RB,
+//   rH = rs/d - rz + M rX + W rY,  oZ = -T^-1 rH,  oX = -K rX - M^T oZ - N rY,  oY = S11^-1 rY - N^T rX - W^T oZ,  ds = (-rs - oZ)/d,
+// the block's vectors in LDS.  Within a block every element of M^T, Kneg, W, NTn and S11i is read from the blob ONCE and
+// meets all RB vectors (the products below keep RB accumulators per output); the solves on the register-resident inverse
+// factor run one right-hand side at a time -- nothing is streamed there.  The products are VALU.
+//
+// Column-parallel, two matrices with one block of vectors (block_matTvec2): outA[k * ldA + c] (opA)= sum_r MatA[r][c] v_k[r]
+// and the same for B, k < RB.  The vectors are INTERLEAVED, vecI[r * RB + k]: the RB values a matrix element meets are one
+// run of LDS (wave-uniform 128-bit reads), RB FMAs per load of the matrix.
+template <class T, int MODEA, int MODEB, int RB, int D>
+QPX_DEV void block_matTvec2_rb(const Block& blk, T* outA, int ldA, const T* MatA, int colsA, T* outB, int ldB, const T* MatB,
+                               int colsB, const T* vecI, int rows)
+{
+    static_assert(RB % 4 == 0, "blocks of four right-hand sides");
+    const int colsAP = (colsA + 63) & ~63;                      // B's columns start at a wave boundary
+    for (int cc = blk.tid; cc < colsAP + colsB; cc += blk.nt) {
+        const bool isA = cc < colsAP;
+        const int c = isA ? cc : cc - colsAP, cols = isA ? colsA : colsB;
+        if (isA && c >= colsA) continue;
+        const T* col = (isA ? MatA : MatB) + c;
+        T acc[RB];
+#pragma unroll
+        for (int k = 0; k < RB; ++k) acc[k] = T(0);
+        // (the last, partial batch too is D unconditional loads -- of the last row again, times zero)
+        for (int r = 0; r < rows; r += D) {
+            T mv[D];
+#pragma unroll
+            for (int u = 0; u < D; ++u) mv[u] = col[(size_t)(r + u < rows ? r + u : rows - 1) * cols];
+#pragma unroll
+            for (int u = 0; u < D; ++u) {
+                const int ru = r + u < rows ? r + u : rows - 1;
+                const T mu = r + u < rows ? mv[u] : T(0);
+#pragma unroll
+                for (int k4 = 0; k4 < RB; k4 += 4) {
+                    T x[4];
+                    ld4(vecI + (size_t)ru * RB + k4, x);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) acc[k4 + k] = fma_(mu, x[k], acc[k4 + k]);
+                }
+            }
+        }
+        T* o = (isA ? outA : outB) + c;
+        const int ld = isA ? ldA : ldB, mode = isA ? MODEA : MODEB;
+#pragma unroll
+        for (int k = 0; k < RB; ++k) o[k * ld] = mode == 0 ? acc[k] : (mode == 1 ? o[k * ld] + acc[k] : o[k * ld] - acc[k]);
+    }
+}
+
+// Row dots on tiles of 16 rows (block_matvec16) with a block of vectors: out[k * ldo + r] (op)= sum_c Mat[r][c] vec[k * ldv + c],
+// k < RB; lane (g, c) of a wave takes rows r0 + g + 4 r and the columns c, c + 16, ...; the 4 x RB sums over a row's
+// sixteen lanes are DPP steps.
+template <class T, int MODE /*0: =, 1: +=, 2: -=*/, int RB>
+QPX_DEV void block_matvec16_rb(const Block& blk, T* out, int ldo, const T* Mat, const T* vec, int ldv, int rows, int cols)
+{
+    const int lane = blk.lane(), g = lane >> 4, c = lane & 15, w = blk.uniform(blk.wave()), nw = blk.nwaves();
+    for (int r0 = 16 * w; r0 < rows; r0 += 16 * nw) {
+        T acc[4][RB];
+        const T* rowp[4];
+        bool live[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = r0 + g + 4 * r;
+            live[r] = row < rows;
+            rowp[r] = Mat + (size_t)(live[r] ? row : rows - 1) * cols;       // clamped: loads stay unconditional
+#pragma unroll
+            for (int k = 0; k < RB; ++k) acc[r][k] = T(0);
+        }
+        for (int c0 = 0; c0 < cols; c0 += 64) {
+            T mv[4][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int col = c0 + 16 * j + c;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mv[j][r] = rowp[r][col < cols ? col : cols - 1];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int col = c0 + 16 * j + c;
+#pragma unroll
+                for (int k = 0; k < RB; ++k) {
+                    const T x = col < cols ? vec[(size_t)k * ldv + col] : T(0);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[r][k] = fma_(mv[j][r], x, acc[r][k]);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int k = 0; k < RB; ++k) {
+                T v = acc[r][k];
+                v += blk.template xor16<1>(v);
+                v += blk.template xor16<2>(v);
+                v += blk.template xor16<7>(v);
+                v += blk.template xor16<15>(v);
+                if (c == 0 && live[r]) {
+                    T* o = out + (size_t)k * ldo + r0 + g + 4 * r;
+                    *o = MODE == 0 ? v : (MODE == 1 ? *o + v : *o - v);
+                }
+            }
+    }
+}
+
+// out_k[i] += sum_r Mat[i * si + r * sr] y_k[r] for the small blocks of the equality constraints (r < q; yI interleaved as
+// above): thread per output i, the matrix elements of its row / column read once, RB accumulators.
+template <class T, int RB>
+QPX_DEV void block_small_rb(const Block& blk, T* out, int ldo, const T* Mat, size_t si, size_t sr, const T* yI, int outs, int q)
+{
+    for (int i = blk.tid; i < outs; i += blk.nt) {
+        T acc[RB];
+#pragma unroll
+        for (int k = 0; k < RB; ++k) acc[k] = out[(size_t)k * ldo + i];
+        for (int r = 0; r < q; ++r) {
+            const T w = Mat[i * si + r * sr];
+#pragma unroll
+            for (int k = 0; k < RB; ++k) acc[k] = fma_(w, yI[(size_t)r * RB + k], acc[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < RB; ++k) out[(size_t)k * ldo + i] = acc[k];
+    }
+}
+
+template <class T, class Mat, int RB, class P>
+QPX_DEV void kkt_multi_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, const P& g)
+{
+    constexpr int M8 = Mat::MP, NT = Mat::NT;
+    const int n = a.n, m = a.m, q = a.q, K = a.K, io32 = a.io32;
+    const int nP = (int)align4((size_t)n), qP = (int)align4((size_t)q);
+    const FacLayout lay = fac_layout(n, m, q, a.images);
+    const T* F = a.fac + (size_t)qp * a.fac_stride;
+    T* rd = lds;                  // lds_elems_kkt_multi
+    T* vD = rd + M8;              // 1/d, 1 on the pad
+    T* vTm = vD + M8;
+    T* bRX = vTm + M8;            // the block's rx, interleaved [i * RB + k]
+    T* bRY = bRX + RB * nP;       // ry, interleaved
+    T* bRH = bRY + RB * qP;       // right-hand sides of the solves [k * M8 + i]
+    T* bDZ = bRH + RB * M8;       // dz [k * M8 + i]
+    T* bDX = bDZ + RB * M8;       // dx [k * nP + i]
+    T* bDY = bDX + RB * nP;       // dy [k * qP + i]
+    T* scr = bDY + RB * qP;       // Mat::scratch_elems()
+
+    const In<T> dg(a.d, (size_t)qp * m, io32);
+    for (int i = b.tid; i < M8; i += NT) vD[i] = i < m ? T(1) / dg[i] : T(1);
+    Mat::sync(b);
+    typename Mat::Regs E;
+    const bool ok = kkt_factor<T, Mat>(b, g, E, Mat::image(F, lay), vD, scr, rd, m, [] {});
+    if (!ok && b.tid == 0 && a.status) a.status[qp] |= QPX_ST_KKT_BREAKDOWN;
+
+    // (B, K, .) arrays, a QP's K vectors contiguous: element idx of the block that starts at right-hand side k0 is vector
+    // k0 + idx / len, entry idx % len
+    const size_t ox = (size_t)qp * K * n, om = (size_t)qp * K * m, oq = (size_t)qp * K * q;
+#pragma unroll 1
+    for (int k0 = 0; k0 < K; k0 += RB) {
+        const int kb = K - k0 < RB ? K - k0 : RB;       // the last block may be partial: its other vectors are zeros
+        const In<T> rxg(a.rx, ox + (size_t)k0 * n, io32), rsg(a.rs, om + (size_t)k0 * m, io32);
+        const In<T> rzg(a.rz, om + (size_t)k0 * m, io32), ryg(q > 0 ? a.ry : nullptr, oq + (size_t)k0 * q, io32);
+        for (int idx = b.tid; idx < RB * n; idx += NT) {
+            const int k = idx / n, i = idx - k * n;
+            bRX[i * RB + k] = (rxg && k < kb) ? rxg[idx] : T(0);
+        }
+        for (int idx = b.tid; idx < RB * q; idx += NT) {
+            const int k = idx / q, i = idx - k * q;
+            bRY[i * RB + k] = (ryg && k < kb) ? ryg[idx] : T(0);
+        }
+        for (int idx = b.tid; idx < RB * M8; idx += NT) {
+            const int k = idx / M8, i = idx - k * M8;
+            T rhs = T(0);
+            if (k < kb && i < m) rhs = (rsg ? rsg[k * m + i] * vD[i] : T(0)) - (rzg ? rzg[k * m + i] : T(0));
+            bRH[idx] = rhs;
+        }
+        Mat::sync(b);
+        // rH += M rX and oX = -K rX, both from one pass over the rows of M^T and Kneg; rH += W rY
+        block_matTvec2_rb<T, 1, 0, RB, 8>(b, bRH, M8, F + lay.MT, m, bDX, nP, F + lay.Kneg, n, bRX, n);
+        if (q > 0) {
+            Mat::sync(b);
+            block_small_rb<T, RB>(b, bRH, M8, F + lay.W, (size_t)q, (size_t)1, bRY, m, q);
+        }
+        Mat::sync(b);
+#pragma unroll 1
+        for (int k = 0; k < RB; ++k) {
+            if (ok && k < kb) Mat::solve_neg(b, g, E, rd, m, bRH + k * M8, bDZ + k * M8, vTm, scr);
+            else
+                for (int i = b.tid; i < M8; i += NT) bDZ[k * M8 + i] = T(0);      // (a breakdown returns zeros for dz, as the single solve)
+        }
+        Mat::sync(b);
+        // oX -= M^T oZ;  oX += NTn^T rY (NTn = -N^T);  oY = S11^-1 rY + NTn rX - W^T oZ
+        block_matvec16_rb<T, 2, RB>(b, bDX, nP, F + lay.MT, bDZ, M8, n, m);
+        if (q > 0) {
+            Mat::sync(b);
+            block_small_rb<T, RB>(b, bDX, nP, F + lay.NTn, (size_t)1, (size_t)n, bRY, n, q);
+            for (int r = b.tid; r < q; r += NT) {
+                T acc[RB];
+#pragma unroll
+                for (int k = 0; k < RB; ++k) acc[k] = T(0);
+                for (int c2 = 0; c2 < q; ++c2) {
+                    const T w = F[lay.S11i + (size_t)r * q + c2];
+#pragma unroll
+                    for (int k = 0; k < RB; ++k) acc[k] = fma_(w, bRY[c2 * RB + k], acc[k]);
+                }
+                for (int c2 = 0; c2 < n; ++c2) {
+                    const T w = F[lay.NTn + (size_t)r * n + c2];
+#pragma unroll
+                    for (int k = 0; k < RB; ++k) acc[k] = fma_(w, bRX[c2 * RB + k], acc[k]);
+                }
+                for (int j = 0; j < m; ++j) {
+                    const T w = -F[lay.W + (size_t)j * q + r];
+#pragma unroll
+                    for (int k = 0; k < RB; ++k) acc[k] = fma_(w, bDZ[k * M8 + j], acc[k]);
+                }
+#pragma unroll
+                for (int k = 0; k < RB; ++k) bDY[k * qP + r] = acc[k];
+            }
+        }
+        Mat::sync(b);
+        for (int idx = b.tid; idx < kb * n; idx += NT) {
+            const int k = idx / n, i = idx - k * n;
+            put_(a.dx, io32, ox + (size_t)k0 * n + idx, bDX[k * nP + i]);
+        }
+        if (a.dz || a.ds)
+            for (int idx = b.tid; idx < kb * m; idx += NT) {
+                const int k = idx / m, i = idx - k * m;
+                const T dzv = bDZ[k * M8 + i];
+                if (a.dz) put_(a.dz, io32, om + (size_t)k0 * m + idx, dzv);
+                if (a.ds) put_(a.ds, io32, om + (size_t)k0 * m + idx, (-(rsg ? rsg[idx] : T(0)) - dzv) * vD[i]);
+            }
+        if (q > 0 && a.dy)
+            for (int idx = b.tid; idx < kb * q; idx += NT) {
+                const int k = idx / q, i = idx - k * q;
+                put_(a.dy, io32, oq + (size_t)k0 * q + idx, bDY[k * qP + i]);
+            }
+        Mat::sync(b);           // the block's vectors are free for the next one
+    }
+}
+
+template <class T, class Mat, int RB>
+QPX_DEV void kkt_multi_body(const Block& b, const KktArgs<T>& a, int qp, T* lds)
+{
+    typename Mat::Pos g(b);
+    g.assign(b, reinterpret_cast<int*>(lds));
+    Mat::with_role(g, [&](const auto& gp) { kkt_multi_role<T, Mat, RB>(b, a, qp, lds, gp); });
+}
+
+// (NBL >= kKktMultiRole: the multi-right-hand-side role of the form with NBL - kKktMultiRole blocks, qpx_forms.h)
 template <class T, int GS, int NBL, bool kBackward>
 QPX_DEV void kkt_grid_body(const Block& b, const KktArgs<T>& a, int qp, T* lds)
 {
-    kkt_mat_body<T, GridMat<T, GS, NBL>, kBackward>(b, a, qp, lds);
+    if constexpr (NBL >= kKktMultiRole) kkt_multi_body<T, GridMat<T, GS, NBL - kKktMultiRole>, kKktMultiRB>(b, a, qp, lds);
+    else kkt_mat_body<T, GridMat<T, GS, NBL>, kBackward>(b, a, qp, lds);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2053,6 +2310,17 @@ QPX_LAYOUT_HD size_t lds_elems_kkt_grid(int gs, int nbl, int n, int q)
 {
     const size_t mg = (size_t)gs * nbl;
     return lds_elems_kkt_mat(mg, 2 * mg + 4 + (size_t)nbl * gs * gs, n, q);
+}
+// ... of its multi-right-hand-side role (kkt_multi_role): rd, 1/d, a temporary; per right-hand side of a block rx, dx (n),
+// ry, dy (q), the solve's right-hand side and dz (mp); the scratch
+QPX_LAYOUT_HD size_t lds_elems_kkt_multi(size_t mp, size_t scratch, int n, int q, int rb)
+{
+    return 3 * mp + 2 * (size_t)rb * (align4((size_t)n) + align4((size_t)q) + mp) + scratch;
+}
+QPX_LAYOUT_HD size_t lds_elems_kkt_multi_grid(int gs, int nbl, int n, int q)
+{
+    const size_t mg = (size_t)gs * nbl;
+    return lds_elems_kkt_multi(mg, 2 * mg + 4 + (size_t)nbl * gs * gs, n, q, kKktMultiRB);
 }
 
 }  // namespace qpx

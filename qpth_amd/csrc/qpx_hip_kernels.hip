@@ -79,7 +79,8 @@ template <class T, int NBL, int NS> int launch_ipm_grid(const IpmArgs<T>& a, siz
 #define QPX_INST(NBL, NS) template int launch_ipm_grid<QPX_TU_REAL, NBL, NS>(const IpmArgs<QPX_TU_REAL>&, size_t, void*);
 QPX_FORMS_IPM_GRID(QPX_INST)
 #elif QPX_TU_KERNEL == 7
-template <class T, int NBL, bool kBw> __global__ __launch_bounds__(256, (NBL <= 7 ? 2 : 1)) void k_kkt_grid(KktArgs<T> a)
+// (NBL >= kKktMultiRole: the form's multi-right-hand-side role, qpx_forms.h)
+template <class T, int NBL, bool kBw> __global__ __launch_bounds__(256, (NBL % kKktMultiRole <= 7 ? 2 : 1)) void k_kkt_grid(KktArgs<T> a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char qpx_smem[];
     const Block b{(int)threadIdx.x, (int)blockDim.x};
@@ -91,7 +92,8 @@ template <class T, int NBL, bool kBw> int launch_kkt_grid(const KktArgs<T>& a, s
 }
 #define QPX_INST(NBL)                                                                               \
     template int launch_kkt_grid<QPX_TU_REAL, NBL, false>(const KktArgs<QPX_TU_REAL>&, size_t, void*); \
-    template int launch_kkt_grid<QPX_TU_REAL, NBL, true>(const KktArgs<QPX_TU_REAL>&, size_t, void*);
+    template int launch_kkt_grid<QPX_TU_REAL, NBL, true>(const KktArgs<QPX_TU_REAL>&, size_t, void*);     \
+    template int launch_kkt_grid<QPX_TU_REAL, kKktMultiRole + NBL, false>(const KktArgs<QPX_TU_REAL>&, size_t, void*);
 QPX_FORMS_KKT_GRID(QPX_INST)
 // the finishing stage (qpx_polish) on the thread grid
 template <class T, int NBL> __global__ __launch_bounds__(256) void k_polish_grid(PolishArgs<T> a)
@@ -196,7 +198,8 @@ template <int NBL, int NW, bool kBw, bool CH> int launch_kkt_tile(const KktArgs<
 }
 #define QPX_INSTK(NBL, NW, CH)                                                                     \
     template int launch_kkt_tile<NBL, NW, false, CH>(const KktArgs<double>&, size_t, void*);       \
-    template int launch_kkt_tile<NBL, NW, true, CH>(const KktArgs<double>&, size_t, void*);
+    template int launch_kkt_tile<NBL, NW, true, CH>(const KktArgs<double>&, size_t, void*);        \
+    template int launch_kkt_tile<kKktMultiRole + NBL, NW, false, CH>(const KktArgs<double>&, size_t, void*);
 #if !defined(QPX_TILE_ONLY)
 QPX_FORMS_KKT_TILE(QPX_INSTK)
 #endif

@@ -158,6 +158,9 @@ template <class T> struct KktArgs {
     // backward with cotangents on the multipliers (qpx_backward_duals): rz = dl_dlam (B,m), ry = dl_dnu (B,q) beside
     // rx = dl_dz; NULL = zeros (and then dl_dz may be NULL too); rs stays zero
     const T *dl_dlam = nullptr, *dl_dnu = nullptr;
+    // the multi-right-hand-side role (qpx_factor_solve_kkt_multi, kkt_multi_role): K > 0 right-hand sides per QP -- rx, rs, rz,
+    // ry and dx, ds, dz, dy are (B, K, .), a QP's K vectors contiguous; one d (B, m) and one factorisation for all of them
+    int K = 0;
 };
 
 // The finishing stage (qpx_polish, include/qpx.h): iterations of the reference's loop in the ORIGINAL variables

@@ -1320,10 +1320,17 @@ QPX_LAYOUT_HD size_t lds_elems_kkt_tile(int nbl, int nw, int n, int q, bool chai
     return lds_elems_kkt_mat(16 * (size_t)nbl, tile_scratch_elems(nbl, chain ? nw - 1 : nw, chain), n, q);
 }
 
+QPX_LAYOUT_HD size_t lds_elems_kkt_multi_tile(int nbl, int nw, int n, int q, bool chain = false)
+{
+    return lds_elems_kkt_multi(16 * (size_t)nbl, tile_scratch_elems(nbl, chain ? nw - 1 : nw, chain), n, q, kKktMultiRB);
+}
+
+// (NBL >= kKktMultiRole: the multi-right-hand-side role of the form with NBL - kKktMultiRole tile rows, qpx_forms.h)
 template <int NBL, int NW, bool kBackward, bool CH = false>
 QPX_DEV void kkt_tile_body(const Block& b, const KktArgs<double>& a, int qp, double* lds)
 {
-    kkt_mat_body<double, TileMat<NBL, NW, CH>, kBackward>(b, a, qp, lds);
+    if constexpr (NBL >= kKktMultiRole) kkt_multi_body<double, TileMat<NBL - kKktMultiRole, NW, CH>, kKktMultiRB>(b, a, qp, lds);
+    else kkt_mat_body<double, TileMat<NBL, NW, CH>, kBackward>(b, a, qp, lds);
 }
 
 template <int NBL, int NW, int NS, bool CH = false>

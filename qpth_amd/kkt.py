@@ -14,6 +14,8 @@ import torch
 
 from . import _lib
 
+MULTI_RHS_BLOCK = 4      # right-hand sides per block of qpx_factor_solve_kkt_multi, every kernel form (csrc/qpx_forms.h: kKktMultiRB)
+
 _STALL_POLICY = None     # None = automatic (reference counter for B == 1, floor rule otherwise)
 
 
@@ -289,6 +291,54 @@ a non-zero diagonal.
             self.lib.factor_solve_kkt(B, n, m, q, self.blob, self.sfac, d, self._vec(rx, n, "rx"), self._vec(rs, m, "rs"),
                                       self._vec(rz, m, "rz"), self._vec(ry, q, "ry"), dx, ds, dz, dy, self.status,
                                       refine=refine, Q=self.Q, G=self.G, A=self.A, wide=self.wide)
+        return dx, ds, dz, dy
+
+    def _vecs(self, X, K, k, what):
+        """dense (B,K,k) contiguous tensor or None: the K-stacked right-hand sides of solve_kkt_many"""
+        if X is None or X.nelement() == 0 or k == 0:
+            return None
+        if X.dtype != self.dtype or X.device != self.device:
+            raise RuntimeError("qpth_amd: %s is %s on %s, the factors were built for %s on %s"
+                               % (what, X.dtype, X.device, self.dtype, self.device))
+        if tuple(X.shape) != (self.B, K, k):
+            raise RuntimeError("qpth_amd: %s has shape %s, expected (%d, %d, %d)" % (what, tuple(X.shape), self.B, K, k))
+        return X.contiguous()
+
+    def solve_kkt_many(self, d, rx, rs, rz, ry, refine=0):
+        """factor_kkt ONCE + solve_kkt for K right-hand sides per QP: rx (B,K,n), rs, rz (B,K,m), ry (B,K,q), each None = zeros
+        (not all of them); d (B,m) as for solve_kkt.  Returns (dx, ds, dz, dy) of shapes (B,K,.), dy None without equalities.
+        One launch and one factorisation of T = R + diag(1/d) per QP (qpx_factor_solve_kkt_multi) where the thread-grid /
+        tile kernels serve the size and refine == 0.  Otherwise -- the large-QP family (nz+neq+nineq > 208), refine > 0 --
+        the same result costs K launches of solve_kkt on slices, each with a factorisation of its own.  No host sync."""
+        B, n, m, q = self.B, self.n, self.m, self.q
+        dt, dev = self.dtype, self.device
+        given = [X for X in (rx, rs, rz, ry if q else None) if X is not None and X.nelement() > 0]
+        if not given:
+            raise RuntimeError("qpth_amd: solve_kkt_many needs at least one of rx, rs, rz, ry")
+        if given[0].dim() != 3:
+            raise RuntimeError("qpth_amd: right-hand sides of solve_kkt_many are (B, K, .), got %s" % (tuple(given[0].shape),))
+        K = given[0].size(1)
+        if K < 1:
+            raise RuntimeError("qpth_amd: solve_kkt_many needs K >= 1 right-hand sides")
+        d = self._vec(d, m, "d")
+        rx, rs, rz, ry = self._vecs(rx, K, n, "rx"), self._vecs(rs, K, m, "rs"), self._vecs(rz, K, m, "rz"), self._vecs(ry, K, q, "ry")
+        dx = torch.empty(B, K, n, dtype=dt, device=dev)
+        ds = torch.empty(B, K, m, dtype=dt, device=dev)
+        dz = torch.empty(B, K, m, dtype=dt, device=dev)
+        dy = torch.empty(B, K, q, dtype=dt, device=dev) if q else None
+        code = _lib.QPX_F32_WIDE if self.wide else (_lib.QPX_F64 if dt == torch.float64 else _lib.QPX_F32)
+        with self._knob():
+            one_launch = refine == 0 and bool(self.lib.dll.qpx_multi_supported(code, n, m, q))
+            if one_launch:
+                self.lib.factor_solve_kkt_multi(B, n, m, q, K, self.blob, self.sfac, d, rx, rs, rz, ry, dx, ds, dz, dy,
+                                                self.status, wide=self.wide)
+        if not one_launch:
+            for k in range(K):
+                cut = [None if X is None else X[:, k] for X in (rx, rs, rz, ry)]
+                out = self.solve_kkt(d, *cut, refine=refine)
+                for dst, src in zip((dx, ds, dz, dy), out):
+                    if dst is not None:
+                        dst[:, k] = src
         return dx, ds, dz, dy
 
     # -- KKTSolvers.IR_UNOPT (batch.py:244-270) as a finishing stage --------------------------------

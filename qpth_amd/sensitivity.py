@@ -1,0 +1,145 @@
+"""Many vector-Jacobian products at ONE solution of a batch of QPs: Jacobians of the solution and of the multipliers.
+
+    sol = qpth_amd.sensitivity.solve(Q, p, G, h, A, b)        # the forward of QPFunction, state kept
+    J = sol.jacobian(of=("z", "lam"), wrt=("p", "h"))         # J["z", "p"][b, i, j] = d zhat_i / d p_j
+    g = sol.vjp_many(dl_dz=V)                                 # V (B, K, n): K cotangents per QP -> g["p"] (B, K, n), ...
+
+`QPFunction`'s backward yields one product per launch, and every launch factors T = R + diag(1/d) again although the matrix
+depends on the solution alone.  Here the K right-hand sides of a QP go through ONE launch and ONE factorisation
+(KKTFactors.solve_kkt_many -> qpx_factor_solve_kkt_multi).  `torch.autograd.grad(..., is_grads_batched=True)` and
+`torch.autograd.functional.jacobian(..., vectorize=True)` cannot do this: they hand backward a vmap-batched tensor without
+storage, which has no pointer to give to a kernel.
+
+An analysis interface, not an autograd node: every output is detached, and `QPFunction` itself is unchanged.
+"""
+import torch
+
+from . import _lib
+from .kkt import KKTFactors
+from .qp import _print_trace, f64_arithmetic_serves
+from .solvers.pdipm import batch as pdipm_b
+from .util import expandParam, extract_nBatch
+
+_VECTORS = ("p", "h", "b")
+_MATRICES = ("Q", "G", "A")
+
+
+class QPSolution:
+    """What the forward of QPFunction leaves behind: zhat (B,n), nu (B,q), lam, slacks (B,m), the factors (KKTFactors) and
+    the parameters expanded to the batch (`params`: Q, p, G, h, A, b; `shared`: which of them the batch shares)."""
+
+    def __init__(self, fac, res, params, shared, refine):
+        self.fac = fac
+        self.zhat, self.nu, self.lam, self.slacks = res.zhat, res.nu, res.lam, res.slacks
+        self.params = dict(zip(("Q", "p", "G", "h", "A", "b"), params))
+        self.shared = dict(zip(("Q", "p", "G", "h", "A", "b"), shared))
+        self.refine = refine          # the backward's rule (qp.py): one in-kernel refinement step where the forward polished
+
+    def vjp_many(self, dl_dz=None, dl_dlam=None, dl_dnu=None, want=_VECTORS):
+        """K vector-Jacobian products per QP.  Cotangents dl_dz (B,K,n), dl_dlam (B,K,m), dl_dnu (B,K,q): None = zeros, pass
+        at least one.  The backward's KKT system (qp.py:148-155), d = clamp(lam, 1e-8) / clamp(slacks, 1e-8), with the
+        right-hand sides (dl_dz, 0, dl_dlam, dl_dnu), solved for all K in one launch (KKTFactors.solve_kkt_many).
+        Returns a dict over `want` of K-stacked gradients: "p": dx (B,K,n), "h": -dz (B,K,m), "b": -dy (B,K,q), and the
+        formulas of qpx_backward_duals for the matrices, "Q": 1/2 (dx zhat' + zhat dx') (B,K,n,n), "G": dz zhat' + lam dx'
+        (B,K,m,n), "A": dy zhat' + nu dx' (B,K,q,n).  The matrix gradients are composed on the host by torch.einsum and are
+        bound by memory traffic: B K n n elements each -- 41 MB for "Q" in float64 at B = 512, K = n = 100, written once
+        and, for a shared parameter, read again by the mean.  A parameter the batch shares gets the reference's `.mean(0)`
+        over B (qp.py:159-177)."""
+        fac, q = self.fac, self.fac.q
+        bad = [w for w in want if w not in _VECTORS + _MATRICES]
+        if bad:
+            raise ValueError("qpth_amd: vjp_many: unknown parameter(s) %s; choose from %s" % (bad, _VECTORS + _MATRICES))
+        if dl_dz is None and dl_dlam is None and (dl_dnu is None or q == 0):
+            raise RuntimeError("qpth_amd: vjp_many needs at least one of dl_dz, dl_dlam, dl_dnu")
+        d = torch.clamp(self.lam, min=1e-8) / torch.clamp(self.slacks, min=1e-8)            # qp.py:148
+        dx, _, dz, dy = fac.solve_kkt_many(d, dl_dz, None, dl_dlam, dl_dnu if q else None,
+                                           refine=1 if (self.refine > 0 and fac.refine_ok) else 0)
+        B, K = dx.shape[:2]
+        if dy is None:
+            dy = dx.new_zeros(B, K, 0)
+        zh, lam, nu = self.zhat, self.lam, self.nu
+
+        def outer(u, v):                 # u (B,K,r), v (B,c) -> u_k v' (B,K,r,c)
+            return torch.einsum("bkr,bc->bkrc", u, v)
+
+        def outer_t(v, u):               # v (B,r), u (B,K,c) -> v u_k' (B,K,r,c)
+            return torch.einsum("br,bkc->bkrc", v, u)
+
+        out = {}
+        for w in want:
+            if w == "p":
+                g = dx
+            elif w == "h":
+                g = -dz
+            elif w == "b":
+                g = -dy
+            elif w == "Q":
+                g = 0.5 * (outer(dx, zh) + outer_t(zh, dx))
+            elif w == "G":
+                g = outer(dz, zh) + outer_t(lam, dx)
+            else:
+                g = outer(dy, zh) + outer_t(nu, dx)
+            out[w] = (g.mean(0) if self.shared[w] else g).detach()
+        return out
+
+    def jacobian(self, of=("z",), wrt=_VECTORS):
+        """Jacobians of the solution -- and of the multipliers: `of` may add "lam" and "nu" -- with respect to the vector
+        parameters in `wrt`, a dict keyed (of, wrt): J["z","p"] (B,n,n) with [b,i,j] = d zhat_i / d p_j, J["z","h"] (B,n,m),
+        J["z","b"] (B,n,q), J["lam","h"] (B,m,m), ...  vjp_many with identity cotangents: K = n (+ m + q) right-hand sides
+        per QP, still one launch.  (The Jacobian with respect to a parameter the batch shares is the mean over the batch of
+        the per-QP Jacobians, as vjp_many returns it.)"""
+        fac = self.fac
+        B, n, m, q = fac.B, fac.n, fac.m, fac.q
+        of = tuple(of)
+        if not of or any(o not in ("z", "lam", "nu") for o in of):
+            raise ValueError("qpth_amd: jacobian: `of` is a non-empty subset of ('z', 'lam', 'nu'), got %s" % (of,))
+        if any(w not in _VECTORS for w in wrt):
+            raise ValueError("qpth_amd: jacobian: only the vector parameters %s are allowed in `wrt`, got %s" % (_VECTORS, tuple(wrt)))
+        sizes = {"z": n, "lam": m, "nu": q}
+        rows, K = {}, 0
+        for o in ("z", "lam", "nu"):
+            if o in of and sizes[o] > 0:
+                rows[o] = (K, K + sizes[o])
+                K += sizes[o]
+        dt, dev = self.zhat.dtype, self.zhat.device
+
+        def identity_block(o):
+            if o not in rows:
+                return None
+            c = torch.zeros(B, K, sizes[o], dtype=dt, device=dev)
+            r0, r1 = rows[o]
+            c[:, r0:r1] = torch.eye(sizes[o], dtype=dt, device=dev)
+            return c
+
+        g = self.vjp_many(identity_block("z"), identity_block("lam"), identity_block("nu"), want=tuple(wrt))
+        J = {}
+        for o in of:
+            r0, r1 = rows.get(o, (0, 0))
+            for w in wrt:
+                J[o, w] = g[w][..., r0:r1, :]
+        return J
+
+
+def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd=True, verbose=-1):
+    """The forward of QPFunction(eps, verbose, notImprovedLim, maxIter, check_Q_spd)(Q, p, G, h, A, b) with its defaults for
+    float32 (float64 arithmetic where f64_arithmetic_serves, else the float32 kernels + two finishing steps): un-batched
+    parameters are broadcast, a Q that is not SPD raises.  Returns the QPSolution; nothing is recorded for autograd."""
+    with torch.no_grad():
+        nBatch = extract_nBatch(Q, p, G, h, A, b)
+        nineq, nz = G.size(-2), G.size(-1)
+        neq = A.size(-2) if A.nelement() > 0 else 0
+        assert(neq > 0 or nineq > 0)
+        wide = Q.dtype == torch.float32 and f64_arithmetic_serves(nz, nineq, neq, _lib.backend_for(Q))
+        params, shared = zip(*[expandParam(X.detach(), nBatch, nd) for X, nd in zip((Q, p, G, h, A, b), (3, 2, 3, 2, 3, 2))])
+        Qe, pe, Ge, he, Ae, be = params
+        fac = KKTFactors.build(Qe, Ge, Ae, nBatch, wide=wide)
+        res = fac.ipm(pe, he, be, eps, maxIter, notImprovedLim, want_trace=(verbose == 1))
+        refine = 2 if (Q.dtype == torch.float32 and not wide) else 0
+        if refine > 0:
+            res = fac.polish(pe, he, be, res, steps=refine, refine=0)
+        fac.raise_on_failure(check_Q_spd)
+        if verbose == 1:
+            _print_trace(res)
+        if verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
+            print(pdipm_b.INACC_ERR)
+        return QPSolution(fac, res, params, shared, refine)
