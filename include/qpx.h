@@ -15,6 +15,7 @@
  *   qpx_backward .......... qpth/qp.py:127-182                     QPFunctionFn.backward (per-QP grads)
  *   qpx_backward_duals .... (no reference counterpart)            the same for a loss of (zhat, lam, nu): cotangents on the multipliers
  *   qpx_jvp ............... (no reference counterpart)            QPFunctionFn.jvp: forward mode, the adjoint of qpx_backward(_duals)
+ *   qpx_ipm_warm .......... (no reference counterpart)            qpx_ipm entered at a previous solution's (lam, slacks)
  *   qpx_factor_solve_kkt_multi  (no reference counterpart)       factor_kkt once, solve_kkt for K right-hand sides per QP: Jacobians
  *
  * Conventions
@@ -165,6 +166,25 @@ int qpx_ipm(int dtype, int B, int n, int m, int q,
             void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim, int stall_policy,
             void* zhat, void* nu, void* lam, void* slack,
             int32_t* iters, int32_t* status, void* best_resid, void* trace, qpx_stream_t stream);
+
+/* Additive after v8 (QPX_ABI_VERSION stays 8): qpx_ipm entered at a WARM START -- qpx_ipm's arguments plus lam0, s0 (B,m),
+ * dense, of dtype like lam (float32 under QPX_F32_WIDE): the multipliers and slacks of a previous solution of a nearby batch.
+ * Per QP: if all 2 m entries are finite the loop starts at z = max(lam0, warm_floor), s = max(s0, warm_floor), with
+ * x = x0 - M^T z and nu = nu0 - W^T z implied by z (dual- and equality-feasible by construction): the reference's
+ * start point (batch.py:61-87: one factorisation and one solve) is skipped and the passes begin at 0.  A QP with a NaN or an Inf
+ * among its entries starts exactly as in qpx_ipm.  warm_used (int32[B], may be NULL): 1 where the warm entry was taken, else 0
+ * (written only when lam0, s0 are given).  Stop rules, iters, status bits, trace and outputs: those of qpx_ipm; there is no new
+ * status bit.  lam0 = s0 = NULL IS qpx_ipm; exactly one of them NULL, or a warm_floor that is not finite or <= 0:
+ * QPX_ERR_ARG.  Served where qpx_warm_supported returns 1 under the calling thread's knob: the thread-grid / tile kernels
+ * (nz+neq+nineq <= 208), all three dtypes; the large-QP family (its start point is a batch-wide launch sequence) returns
+ * QPX_ERR_UNSUPPORTED when lam0, s0 are given. */
+int qpx_warm_supported(int dtype, int n, int m, int q);
+int qpx_ipm_warm(int dtype, int B, int n, int m, int q,
+                 const void* p, int64_t sp, const void* h, int64_t sh, const void* b, int64_t sb,
+                 void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim, int stall_policy,
+                 void* zhat, void* nu, void* lam, void* slack,
+                 int32_t* iters, int32_t* status, void* best_resid, void* trace,
+                 const void* lam0, const void* s0, double warm_floor, int32_t* warm_used, qpx_stream_t stream);
 
 /* qpx_pre_factor followed by qpx_ipm on the same stream */
 int qpx_forward(int dtype, int B, int n, int m, int q,

@@ -40,6 +40,9 @@ _SIGNATURES = {
     "qpx_pre_factor": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "qpx_ipm": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d, _i, _i, _i,
                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qpx_warm_supported": (_i, [_i, _i, _i, _i]),
+    "qpx_ipm_warm": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d, _i, _i, _i,
+                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp]),
     "qpx_forward": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                          _vp, _i64, _vp, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qpx_factor_solve_kkt": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -144,8 +147,17 @@ class QpxLib:
 
     # -- batch.py:47-207 ----------------------------------------------------------------
     def ipm(self, B, n, m, q, p, h, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
-            zhat, nu, lam, slack, iters, status, best_resid, trace=None, wide=False):
+            zhat, nu, lam, slack, iters, status, best_resid, trace=None, wide=False,
+            lam0=None, s0=None, warm_floor=1e-2, warm_used=None):
+        """lam0, s0 (B,m) dense: the warm start (qpx_ipm_warm); without them the call is qpx_ipm itself, as before."""
         pp, hp, bp = Param(p, 2), Param(h, 2), Param(b, 2)
+        if lam0 is not None or s0 is not None:
+            self.check(self.dll.qpx_ipm_warm(
+                _code(factors, wide), B, n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
+                _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
+                _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid),
+                _ptr(trace), _ptr(lam0), _ptr(s0), float(warm_floor), _ptr(warm_used), _stream(factors)))
+            return
         self.check(self.dll.qpx_ipm(
             _code(factors, wide), B, n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
             _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),

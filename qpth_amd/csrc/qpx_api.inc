@@ -159,12 +159,14 @@ template <class T>
 int api_ipm(int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
             const void* bb, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
             int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters,
-            int32_t* status, void* best_resid, void* trace, void* stream, int io32 = 0)
+            int32_t* status, void* best_resid, void* trace, void* stream, int io32 = 0,
+            const void* lam0 = nullptr, const void* s0 = nullptr, double warm_floor = 0, int32_t* warm_used = nullptr)
 {
     if (!p || !h || !factors || !zhat || !lam || !slack || !iters || !status || !best_resid ||
         (q > 0 && (!nu || !bb)))
         return QPX_ERR_ARG;
     if (maxIter < 0 || stall_policy < 0 || stall_policy > 2) return QPX_ERR_ARG;
+    if ((lam0 == nullptr) != (s0 == nullptr)) return QPX_ERR_ARG;
     IpmArgs<T> a;
     a.io32 = io32;
     a.B = B; a.n = n; a.m = m; a.q = q;
@@ -174,8 +176,10 @@ int api_ipm(int B, int n, int m, int q, const void* p, int64_t sp, const void* h
     a.eps = (T)eps; a.maxIter = maxIter; a.notImprovedLim = notImprovedLim; a.stall_policy = stall_policy;
     a.zhat = (T*)zhat; a.nu = (T*)nu; a.lam = (T*)lam; a.slack = (T*)slack;
     a.iters = iters; a.status = status; a.best_resid = (T*)best_resid; a.trace = (T*)trace;
+    a.lam0 = (const T*)lam0; a.s0 = (const T*)s0; a.warm_floor = (T)warm_floor; a.warm_used = lam0 ? warm_used : nullptr;
     a.images = blob_images<T>(n, m, q);
     if (a.images == 8) {
+        if (lam0) return QPX_ERR_UNSUPPORTED;             // the large-QP family's start point is a launch sequence of its own: no warm entry (qpx_warm_supported)
         if (sfac == 0 && B > 1) return QPX_ERR_ARG;       // per-QP work matrices live in the blob
         return big_split(B, stream, a.trace == nullptr, [&](int q0, int cnt, void* st, int part, int nparts) {     // trace is indexed [it][B][3]
             IpmArgs<T> s = a;
@@ -527,16 +531,36 @@ int qpx_pre_factor(int dtype, int B, int n, int m, int q, const void* Q, int64_t
                : qpx::api_pre_factor<float>(B, n, m, q, Q, sQ, G, sG, A, sA, factors, status, stream);
 }
 
+int qpx_warm_supported(int dtype, int n, int m, int q)
+{
+    // the thread-grid / tile loop kernels take a warm start (IpmArgs::lam0, s0), in all three dtypes
+    if (qpx::check_dims(dtype, 1, n, m, q) != QPX_OK) return 0;
+    return qpx::use_grid(n, m, q) ? 1 : 0;
+}
+
+int qpx_ipm_warm(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h,
+                 int64_t sh, const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter,
+                 int notImprovedLim, int stall_policy, void* zhat, void* nu, void* lam, void* slack,
+                 int32_t* iters, int32_t* status, void* best_resid, void* trace,
+                 const void* lam0, const void* s0, double warm_floor, int32_t* warm_used, qpx_stream_t stream)
+{
+    const int e = qpx::check_dims(dtype, B, n, m, q);
+    if (e) return e;
+    if (!(warm_floor > 0) || !(warm_floor < __builtin_huge_val())) return QPX_ERR_ARG;      // NaN, Inf, <= 0
+    return dtype != QPX_F32
+               ? qpx::api_ipm<double>(B, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters, status, best_resid, trace, stream, dtype == QPX_F32_WIDE,
+                                      lam0, s0, warm_floor, warm_used)
+               : qpx::api_ipm<float>(B, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters, status, best_resid, trace, stream, 0,
+                                     lam0, s0, warm_floor, warm_used);
+}
+
 int qpx_ipm(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h,
             int64_t sh, const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter,
             int notImprovedLim, int stall_policy, void* zhat, void* nu, void* lam, void* slack,
             int32_t* iters, int32_t* status, void* best_resid, void* trace, qpx_stream_t stream)
 {
-    const int e = qpx::check_dims(dtype, B, n, m, q);
-    if (e) return e;
-    return dtype != QPX_F32
-               ? qpx::api_ipm<double>(B, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters, status, best_resid, trace, stream, dtype == QPX_F32_WIDE)
-               : qpx::api_ipm<float>(B, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters, status, best_resid, trace, stream);
+    return qpx_ipm_warm(dtype, B, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack,
+                        iters, status, best_resid, trace, nullptr, nullptr, 1e-2, nullptr, stream);
 }
 
 int qpx_forward(int dtype, int B, int n, int m, int q, const void* Q, int64_t sQ, const void* p,

@@ -953,9 +953,12 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         if (b.tid == 0) {
             a.iters[qp] = 0;
             put_(a.best_resid, io32, (size_t)qp, Lim<T>::inf());
+            if (a.warm_used) a.warm_used[qp] = 0;
         }
         return;
     }
+    enum { kTau = 0, kBtau, kSigz, kSigs, kBres, kFeasPrev, kAlphaPrev, kMu, kSzdot, kFeas, kResid, kGt1 };
+    enum { kStop = 0, kNnot, kFloor, kSt, kIters, kWarm };
     QPX_PROF_INIT
     // ---- c = h - G x0 = h + M p - W b   (x0 = -K p + N b is formed only at the end)
     for (int i = b.tid; i < n; i += NT) vP[i] = pg[i];
@@ -965,6 +968,16 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         vA[i] = T(1);                     // first use: R 1
     }
     Mat::sync(b);
+    // warm start (IpmArgs): this QP takes (lam0, s0) only if all 2 m entries are finite -- decided by the lead wave here,
+    // read by every wave behind the barrier that ends the prologue's products
+    const In<T> l0g(a.lam0, (size_t)qp * m, io32), s0g(a.s0, (size_t)qp * m, io32);
+    if (a.lam0 && w0) {
+        T ok = T(1);
+        for (int i = lane; i < m; i += kWave)
+            if (!finite_(l0g[i]) || !finite_(s0g[i])) ok = T(0);
+        ok = wave_min(b, ok);
+        if (lane == 0) ctrl[kWarm] = ok > T(0);
+    }
     block_matTvec2<T, 1, 0>(b, vC, F + lay.MT, m, vX0, F + lay.Kneg, n, vP, n);      // c += M p;  x0 = -K p
     if (q > 0) {
         Mat::sync(b);
@@ -984,8 +997,6 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     // iteration, and carried through the factorisation it cost 32 spilled VGPRs (scratch reloads with
     // a memory round trip each) -- measured on MI355X.
     typename Mat::Regs E;
-    enum { kTau = 0, kBtau, kSigz, kSigs, kBres, kFeasPrev, kAlphaPrev, kMu, kSzdot, kFeas, kResid, kGt1 };
-    enum { kStop = 0, kNnot, kFloor, kSt, kIters };
     if (b.tid == 0) {
         sc[kTau] = T(1); sc[kBtau] = T(1); sc[kSigz] = T(0); sc[kSigs] = T(0); sc[kBres] = Lim<T>::inf();
         sc[kFeasPrev] = T(0); sc[kAlphaPrev] = T(0);
@@ -996,6 +1007,27 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         vZ[i] = T(1); vS[i] = T(1); vRZ[i] = T(1); vRS[i] = T(1);
         vDSA[i] = T(0); vRSC[i] = T(0);
     }
+    // ---- the warm entry: z = max(lam0, f), s = max(s0, f), z' = z (sigma_z = sigma_s = 0, tau = 1 as set above): x = x0 - M^T z
+    // and nu = nu0 - W^T z are dual- and equality-feasible by construction, so pass -1 (the start point: one factorisation and
+    // one solve) is not needed and the passes begin at 0.  R 1 is formed in pass -1 only: zeroed, tau sigma_z R 1 must not
+    // meet what LDS held.  The best iterate is taken at pass 0 as ever; it is set here for a breakdown inside that pass.
+    const bool warm = a.lam0 && ctrl[kWarm];
+    if (warm) {
+        const T fl = a.warm_floor;
+        for (int i = b.tid; i < M8; i += NT) {
+            if (i < m) {
+                const T zk = max2_(fl, l0g[i]), sk = max2_(fl, s0g[i]);
+                vZ[i] = zk; vS[i] = sk;
+                vBZ[i] = zk; vBS[i] = sk;
+                vA[i] = zk;
+            } else {
+                vA[i] = T(0);
+            }
+            vR1[i] = T(0);
+        }
+    }
+    if (b.tid == 0 && a.warm_used) a.warm_used[qp] = warm;
+    const int it0 = warm ? 0 : -1;
     Mat::sync(b);
 
     // ---- pass -1 is the start point: T = R + I, z_i = -T^-1 c, s_i = -z_i, shifts (batch.py:61-87),
@@ -1014,7 +1046,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     // the floating-point operations as written: those of the order below.
     typename Mat::Ahead ah;
     Mat::ahead_init(b, g, ah, Rg);
-    for (int it = -1; it < a.maxIter && !stop; ++it) {
+    for (int it = it0; it < a.maxIter && !stop; ++it) {
         const bool first = it < 0;
         Mat::load(b, g, E, Rg);
         QPX_PROF(2)
@@ -1139,7 +1171,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         QPX_PROF(1)
     }
     } else {
-    for (int it = -1; it < a.maxIter && !stop; ++it) {
+    for (int it = it0; it < a.maxIter && !stop; ++it) {
         const bool first = it < 0;
         Mat::load(b, g, E, Rg);
         QPX_PROF(2)

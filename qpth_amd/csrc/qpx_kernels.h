@@ -129,6 +129,12 @@ template <class T> struct IpmArgs {
     T* trace;                             // optional [maxIter][B][3]: pri_resid, dual_resid, mu
     int images;                           // blob family the factors were written in (fac_layout)
     int io32 = 0;                         // T = double only: every array but `fac` is float32 (QPX_F32_WIDE)
+    // warm start (qpx_ipm_warm; thread-grid / tile kernels only): lam0, s0 (B,m) dense, float32 under io32; NULL = the
+    // reference's start point.  A QP whose 2 m entries are all finite enters the loop at z = max(lam0, warm_floor),
+    // s = max(s0, warm_floor), pass 0; any other QP starts cold.  warm_used (B), optional: 1 / 0 per QP
+    const T *lam0 = nullptr, *s0 = nullptr;
+    T warm_floor = T(0);
+    int* warm_used = nullptr;
 };
 
 template <class T> struct KktArgs {

@@ -89,7 +89,8 @@ def solve_sharded(qp_function, Q, p, G, h, A, b, nBatch, gather=True, group=None
     (a QPFunction(...) callable); returns the local zhat and, if gather, the full one.  A callable that returns a tuple
     (QPFunction(duals=True): zhat, nu, lam, slacks) comes back as the local tuple and, if gather, a tuple of the same
     length with every output gathered to the full batch (values only, as for zhat) and None in the place of an empty one
-    (nu without equality constraints)."""
+    (nu without equality constraints).  A QPFunction(warm_start=ws) needs nothing here: every rank passes a holder of its own,
+    which sees that rank's slice of the batch, call after call."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     check_shardable([Q, p, G, h, A, b], nBatch, world)
     lQ, lp, lG, lh, lA, lb = shard_params([Q, p, G, h, A, b], nBatch, rank, world)

@@ -33,7 +33,50 @@ def default_stall_policy(B):
 
 
 class IpmResult:
-    __slots__ = ("zhat", "nu", "lam", "slacks", "iters", "status", "best_resid", "trace")
+    __slots__ = ("zhat", "nu", "lam", "slacks", "iters", "status", "best_resid", "trace", "_warm_used")
+
+    @property
+    def warm_used(self):
+        """int32 (B,): 1 where the loop took the warm entry (KKTFactors.ipm(warm=...)).  A cold call has zeros here, made
+        when first asked for: the cold path pays no launch for them."""
+        if self._warm_used is None:
+            self._warm_used = torch.zeros(self.iters.shape, dtype=torch.int32, device=self.iters.device)
+        return self._warm_used
+
+
+class WarmStart:
+    """The (lam, slacks) of the previous solve of a batch, kept between calls so that the next solve of a nearby batch
+    starts there (QPFunction(warm_start=ws), sensitivity.solve(warm_start=ws)):
+
+        ws = qpth_amd.WarmStart()
+        for step in range(steps):
+            z = QPFunction(warm_start=ws)(Q, p, G, h, A, b)      # first call cold, every later one from the last solution
+
+    A small holder: `lam`, `slacks` are the tensors the last forward produced (detached references, no copy), `used` the
+    int32 (B,) tensor of that forward (1 where the loop took the warm entry; None before the first call), `floor` the
+    value both are floored at on entry.  A holder whose tensors do not match the call -- another (B, nineq), dtype or
+    device -- is ignored (that call is cold) and overwritten.  `clear()` empties it: the next call is cold."""
+
+    def __init__(self, floor=1e-2):
+        if not (floor > 0 and floor < float("inf")):
+            raise ValueError("qpth_amd: WarmStart floor must be positive and finite, got %r" % (floor,))
+        self.floor = float(floor)
+        self.clear()
+
+    def clear(self):
+        self.lam = self.slacks = self.used = None
+
+    def matches(self, B, m, dtype, device):
+        return all(X is not None and tuple(X.shape) == (B, m) and X.dtype == dtype and X.device == device
+                   for X in (self.lam, self.slacks))
+
+    def take(self, res):
+        """keep what a forward produced (KKTFactors.ipm's / polish's result)"""
+        self.lam, self.slacks, self.used = res.lam.detach(), res.slacks.detach(), res.warm_used
+
+    def pair(self, B, m, dtype, device):
+        """(lam, slacks) for KKTFactors.ipm(warm=...), or None when the holder is empty or of another batch"""
+        return (self.lam, self.slacks) if self.matches(B, m, dtype, device) else None
 
 
 def _batch_of(*params3):
@@ -247,10 +290,15 @@ a non-zero diagonal.
         return X.contiguous()
 
     # -- forward (batch.py:47-207) -------------------------------------------------------
-    def ipm(self, p, h, b, eps=1e-12, maxIter=20, notImprovedLim=3, stall_policy=None, want_trace=False):
+    def ipm(self, p, h, b, eps=1e-12, maxIter=20, notImprovedLim=3, stall_policy=None, want_trace=False,
+            warm=None, warm_floor=1e-2):
         """The IPM loop (batch.py:47-207), one kernel launch, no host sync.  `result.status` IS the factors'
         status array: the loop ORs its bits (breakdown, maxIter, inaccurate) into the pre-factorisation's,
-        so repeated calls on the same factors accumulate them."""
+        so repeated calls on the same factors accumulate them.
+        warm = (lam0, s0), each (B, nineq): the loop starts at z = max(lam0, warm_floor), s = max(s0, warm_floor) instead
+        of the reference's start point (qpx_ipm_warm), QP by QP where all entries are finite.
+        `result.warm_used`, int32 (B,): 1 where it did.  Where the kernel family has no warm entry (qpx_warm_supported: the
+        large-QP family) the call is the cold one and warm_used is zeros -- no error."""
         B, n, m, q = self.B, self.n, self.m, self.q
         dt, dev = self.dtype, self.device
         r = IpmResult()
@@ -262,6 +310,21 @@ a non-zero diagonal.
         r.best_resid = torch.empty(B, dtype=dt, device=dev)
         r.trace = torch.full((maxIter, B, 3), float('nan'), dtype=dt, device=dev) if want_trace else None
         r.status = self.status
+        r._warm_used = None
+        kw = {}
+        if warm is not None:
+            lam0, s0 = warm
+            if not (warm_floor > 0 and warm_floor < float("inf")):
+                raise ValueError("qpth_amd: warm_floor must be positive and finite, got %r" % (warm_floor,))
+            self._check(lam0, m, "warm[0] (lam0)")
+            self._check(s0, m, "warm[1] (s0)")
+            code = _lib.QPX_F32_WIDE if self.wide else (_lib.QPX_F64 if dt == torch.float64 else _lib.QPX_F32)
+            with self._knob():
+                served = bool(self.lib.dll.qpx_warm_supported(code, n, m, q))
+            if served:
+                r._warm_used = torch.empty(B, dtype=torch.int32, device=dev)          # the kernel writes every QP's word
+                kw = dict(lam0=self._vec(lam0, m, "warm[0] (lam0)"), s0=self._vec(s0, m, "warm[1] (s0)"),
+                          warm_floor=warm_floor, warm_used=r._warm_used)
         if stall_policy is None:
             stall_policy = default_stall_policy(B)
         self._check(p, n, "p")
@@ -273,7 +336,7 @@ a non-zero diagonal.
         with self._knob():
             self.lib.ipm(B, n, m, q, p, h, b if q else None, self.blob, self.sfac, eps, maxIter, notImprovedLim,
                          stall_policy, r.zhat, r.nu if q else None, r.lam, r.slacks, r.iters, self.status,
-                         r.best_resid, r.trace, wide=self.wide)
+                         r.best_resid, r.trace, wide=self.wide, **kw)
         return r
 
     # -- factor_kkt + solve_kkt (batch.py:435-470, 349-372) ----------------------------------

@@ -11,6 +11,7 @@ products); state crosses from forward to backward on ctx exactly as in the refer
 Forward mode (torch.autograd.forward_ad, which the reference does not support) is one more launch: QPFunctionFn.jvp solves
 the backward's KKT system with the right-hand side formed from the input tangents (qpx_jvp).
 QPFunction(duals=True) also returns the multipliers, differentiable in both modes: (zhat, nu, lam, slacks).
+QPFunction(warm_start=ws) starts the loop at the previous call's (lam, slacks) kept in a qpth_amd.WarmStart.
 """
 from enum import Enum
 
@@ -51,8 +52,17 @@ def f64_arithmetic_serves(nz, nineq, neq, lib=None):
 
 def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                maxIter=20, solver=QPSolvers.PDIPM_BATCHED,
-               check_Q_spd=True, refine=None, duals=False):
-    """`refine` and `duals` are the arguments the reference does not have.
+               check_Q_spd=True, refine=None, duals=False, warm_start=None):
+    """`refine`, `duals` and `warm_start` are the arguments the reference does not have.
+    warm_start: a qpth_amd.WarmStart, the SAME object on every step of a training loop.  The first call is cold (the holder
+      is empty); every later call enters the PDIPM loop at the previous call's (lam, slacks), floored at `ws.floor`, instead
+      of the reference's start point, and needs about half the iterations while the parameters move by small steps (DESIGN
+      4.7).  The holder then takes this call's lam, slacks (references, detached) and `ws.used`, int32 (nBatch,): 1 where the
+      loop took the warm entry.  A holder of another (nBatch, nineq), dtype or device is ignored -- that call is cold -- and
+      overwritten; sizes of the large-QP family (nz+neq+nineq > 208) always start cold (`ws.used` zeros).  The solution,
+      backward, jvp and duals=True are those of the cold call to the solver's tolerance: they read the solution only.  The
+      external-solver path (solver=QPSolvers.CVXPY) ignores the holder.  Under qpth_amd.dist.solve_sharded each rank's holder
+      sees its own slice.
     duals=True: the call returns (zhat, nu, lam, slacks) -- the reference forward's order (batch.py:47-207) -- instead of
       zhat alone.  zhat, lam (nBatch, nineq) and nu (nBatch, neq) are differentiable in all six parameters, in reverse and in
       forward mode: a loss l(zhat, lam, nu) back-propagates through the same single backward launch, its KKT right-hand side
@@ -95,14 +105,18 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
 
             if solver == QPSolvers.PDIPM_BATCHED:
                 fac = KKTFactors.build(Q, G, A, nBatch, wide=ctx.wide)   # qp.py:93
+                warm = warm_start.pair(nBatch, nineq, Q.dtype, Q.device) if warm_start is not None else None
                 res = fac.ipm(p, h, b, eps, maxIter, notImprovedLim,
-                              want_trace=(verbose == 1))             # qp.py:94-96
+                              want_trace=(verbose == 1), warm=warm,
+                              warm_floor=warm_start.floor if warm is not None else 1e-2)   # qp.py:94-96
                 ctx.refine = (2 if Q.dtype == torch.float32 and not ctx.wide else 0) if refine is None else int(refine)
                 if ctx.refine > 0:
                     # (the solves inside a finishing step are NOT refined: the step's own residuals are exact, and refining
                     # the directions as well changes nothing in the answer -- C2 / C3 float32, two steps: the same error
                     # distribution to three digits -- for 40 % more time per step; profiles/archive/r04f)
                     res = fac.polish(p, h, b, res, steps=ctx.refine, refine=0)
+                if warm_start is not None:
+                    warm_start.take(res)
                 # one small read-back: the reference raises here too (qp.py:81-85, batch.py:379-386)
                 fac.raise_on_failure(check_Q_spd)
                 if verbose == 1:

@@ -120,10 +120,12 @@ class QPSolution:
         return J
 
 
-def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd=True, verbose=-1):
+def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd=True, verbose=-1, warm_start=None):
     """The forward of QPFunction(eps, verbose, notImprovedLim, maxIter, check_Q_spd)(Q, p, G, h, A, b) with its defaults for
     float32 (float64 arithmetic where f64_arithmetic_serves, else the float32 kernels + two finishing steps): un-batched
-    parameters are broadcast, a Q that is not SPD raises.  Returns the QPSolution; nothing is recorded for autograd."""
+    parameters are broadcast, a Q that is not SPD raises.  Returns the QPSolution; nothing is recorded for autograd.
+    warm_start: a qpth_amd.WarmStart, as for QPFunction(warm_start=...) -- the loop starts at the holder's (lam, slacks) and
+    the holder takes this solve's."""
     with torch.no_grad():
         nBatch = extract_nBatch(Q, p, G, h, A, b)
         nineq, nz = G.size(-2), G.size(-1)
@@ -133,10 +135,14 @@ def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd
         params, shared = zip(*[expandParam(X.detach(), nBatch, nd) for X, nd in zip((Q, p, G, h, A, b), (3, 2, 3, 2, 3, 2))])
         Qe, pe, Ge, he, Ae, be = params
         fac = KKTFactors.build(Qe, Ge, Ae, nBatch, wide=wide)
-        res = fac.ipm(pe, he, be, eps, maxIter, notImprovedLim, want_trace=(verbose == 1))
+        warm = warm_start.pair(nBatch, nineq, Q.dtype, Q.device) if warm_start is not None else None
+        res = fac.ipm(pe, he, be, eps, maxIter, notImprovedLim, want_trace=(verbose == 1), warm=warm,
+                      warm_floor=warm_start.floor if warm is not None else 1e-2)
         refine = 2 if (Q.dtype == torch.float32 and not wide) else 0
         if refine > 0:
             res = fac.polish(pe, he, be, res, steps=refine, refine=0)
+        if warm_start is not None:
+            warm_start.take(res)
         fac.raise_on_failure(check_Q_spd)
         if verbose == 1:
             _print_trace(res)

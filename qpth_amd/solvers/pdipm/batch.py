@@ -189,9 +189,11 @@ def kkt_resid_reg(Q_tilde, D_tilde, G, A, eps, dx, ds, dz, dy, rx, rs, rz, ry):
 
 
 def forward(Q, p, G, h, A, b, Q_LU, S_LU, R, eps=1e-12, verbose=0, notImprovedLim=3,
-            maxIter=20, solver=KKTSolvers.LU_PARTIAL, stall_policy=None):
+            maxIter=20, solver=KKTSolvers.LU_PARTIAL, stall_policy=None, warm=None):
     """
     Q_LU, S_LU, R = pre_factor_kkt(Q, G, A)
+    warm = (lam0, s0), each (nBatch, nineq): start the loop at a previous solution's multipliers and slacks instead of the
+    reference's start point (KKTFactors.ipm); the large-QP family starts cold regardless.
     """
     if not isinstance(solver, KKTSolvers):
         raise ValueError("solver must be a KKTSolvers member, got %r" % (solver,))
@@ -200,7 +202,7 @@ def forward(Q, p, G, h, A, b, Q_LU, S_LU, R, eps=1e-12, verbose=0, notImprovedLi
     # LU_FULL and LU_PARTIAL are two elimination orders of one KKT system in the reference (batch.py:313-346 vs
     # 349-372, same iterates to rounding: test.py:222-234); the HIP path has one elimination, the condensed one,
     # and runs it for both.  IR_UNOPT adds what its name promises: steps on the residual of the ORIGINAL system.
-    res = fac.ipm(p, h, b, eps, maxIter, notImprovedLim, stall_policy, want_trace=(verbose == 1))
+    res = fac.ipm(p, h, b, eps, maxIter, notImprovedLim, stall_policy, want_trace=(verbose == 1), warm=warm)
     if solver == KKTSolvers.IR_UNOPT:
         res = fac.polish(p, h, b, res, refine=1)          # (its solves refined as well: solve_kkt_ir is what the name asks for)
     if verbose == 1:
