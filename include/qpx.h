@@ -17,6 +17,7 @@
  *   qpx_jvp ............... (no reference counterpart)            QPFunctionFn.jvp: forward mode, the adjoint of qpx_backward(_duals)
  *   qpx_ipm_warm .......... (no reference counterpart)            qpx_ipm entered at a previous solution's (lam, slacks)
  *   qpx_factor_solve_kkt_multi  (no reference counterpart)       factor_kkt once, solve_kkt for K right-hand sides per QP: Jacobians
+ *   qpx_pre_factor_soft ... (no reference counterpart)            qpx_pre_factor with a quadratic penalty on the violation of chosen rows of G z <= h
  *
  * Conventions
  *   - dtype: QPX_F32 or QPX_F64: every `void*` array below has that element type; or QPX_F32_WIDE (see the enum).
@@ -156,6 +157,22 @@ int qpx_big_gemm_r(int dtype, int B, int n, int m, int q, void* factors, qpx_str
 int qpx_pre_factor(int dtype, int B, int n, int m, int q,
                    const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
                    void* factors, int32_t* status, qpx_stream_t stream);
+
+/* Soft inequality rows (additive after v8; QPX_ABI_VERSION stays 8):
+ *     min 1/2 z'Qz + p'z + 1/2 sum_i rho_i t_i^2   s.t.  Gz <= h + t,  Az = b
+ * pre-factored as the hard QP with two values of the blob changed -- R + diag(w) on the diagonal of every image of
+ * R = G K G^T, and sqrt(|| G^T 1 ||^2 + #{i: w_i > 0}) for || G^T 1 || -- which is exactly the pre-factorisation of the
+ * augmented QP in (z, t) condensed to the nineq rows.  w (B,m) of `dtype` (float32 under QPX_F32_WIDE), w_i = 1 / rho_i,
+ * 0 = a hard row; sw: its batch stride in elements, 0 = shared by the batch; w == NULL is qpx_pre_factor itself, and an
+ * all-zero w writes the same blob bit for bit.  Entries must be finite and >= 0: a QP with any other entry gets
+ * QPX_ST_NONFINITE OR-ed into its status word.  Every consumer of the blob then serves the softened QP as it stands:
+ * qpx_ipm(_warm) returns lam, the violation is t = w lam, and slack = h + t - G zhat; in qpx_backward(_duals) the
+ * gradient with respect to w is -dz lam (dz: the KKT solution the call returns on request), in qpx_jvp a tangent tw
+ * acts as th + tw lam.  NOT for refine > 0 or qpx_polish: they evaluate residuals from the caller's Q, G, A, i.e. of
+ * the hard QP; the host refuses the combination. */
+int qpx_pre_factor_soft(int dtype, int B, int n, int m, int q,
+                        const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
+                        const void* w, int64_t sw, void* factors, int32_t* status, qpx_stream_t stream);
 
 /* forward(Q,p,G,h,A,b,Q_LU,S_LU,R,...): the PDIPM loop on pre-factored QPs.  Outputs in the
  * reference's return order x, y, z, s = zhat (B,n), nu (B,q), lam (B,m), slacks (B,m);

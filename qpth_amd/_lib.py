@@ -38,6 +38,7 @@ _SIGNATURES = {
     "qpx_can_share_factors": (_i, [_i, _i, _i, _i]),
     "qpx_big_gemm_r": (_i, [_i, _i, _i, _i, _i, _vp, _vp]),
     "qpx_pre_factor": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "qpx_pre_factor_soft": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "qpx_ipm": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d, _i, _i, _i,
                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qpx_warm_supported": (_i, [_i, _i, _i, _i]),
@@ -139,8 +140,16 @@ class QpxLib:
         return int(self.dll.qpx_factor_elems(dtype_code, n, m, q))
 
     # -- batch.py:375-429 ---------------------------------------------------------------
-    def pre_factor(self, B, n, m, q, Q, G, A, factors, status, wide=False):
+    def pre_factor(self, B, n, m, q, Q, G, A, factors, status, wide=False, w=None):
+        """w (B,m) or (m,): soft rows, w = 1 / rho, 0 = hard (qpx_pre_factor_soft); without it the call is qpx_pre_factor
+        itself, as before."""
         Qp, Gp, Ap = Param(Q, 3), Param(G, 3), Param(A, 3)
+        if w is not None:
+            wp = Param(w, 2)
+            self.check(self.dll.qpx_pre_factor_soft(
+                _code(factors, wide), B, n, m, q, Qp.ptr, Qp.stride, Gp.ptr, Gp.stride, Ap.ptr, Ap.stride,
+                wp.ptr, wp.stride, _ptr(factors), _ptr(status), _stream(factors)))
+            return
         self.check(self.dll.qpx_pre_factor(
             _code(factors, wide), B, n, m, q, Qp.ptr, Qp.stride, Gp.ptr, Gp.stride, Ap.ptr, Ap.stride,
             _ptr(factors), _ptr(status), _stream(factors)))

@@ -116,11 +116,13 @@ template <class T> inline size_t blob_elems(int n, int m, int q)
 
 template <class T>
 int api_pre_factor(int B, int n, int m, int q, const void* Q, int64_t sQ, const void* G, int64_t sG,
-                   const void* A, int64_t sA, void* factors, int32_t* status, void* stream, int io32 = 0)
+                   const void* A, int64_t sA, void* factors, int32_t* status, void* stream, int io32 = 0,
+                   const void* w = nullptr, int64_t sw = 0)
 {
     if (!Q || !G || !factors || !status || (q > 0 && !A)) return QPX_ERR_ARG;
     PrefactorArgs<T> a;
     a.io32 = io32;
+    a.w = (const T*)w; a.sw = sw;                // soft rows (qpx_pre_factor_soft); NULL: none
     a.B = B; a.n = n; a.m = m; a.q = q;
     a.Q = (const T*)Q; a.G = (const T*)G; a.A = (const T*)A;
     a.sQ = sQ; a.sG = sG; a.sA = sA;
@@ -129,7 +131,8 @@ int api_pre_factor(int B, int n, int m, int q, const void* Q, int64_t sQ, const 
         const size_t fs = big_layout(n, m, q).total;
         return big_split(B, stream, true, [&](int q0, int cnt, void* st, int part, int nparts) {
             return big_pre_factor<T>(cnt, n, m, q, advio(a.Q, (size_t)q0 * sQ, io32), sQ, advio(a.G, (size_t)q0 * sG, io32), sG,
-                                     advio(a.A, (size_t)q0 * sA, io32), sA, (T*)factors + (size_t)q0 * fs, status + q0, st, io32);
+                                     advio(a.A, (size_t)q0 * sA, io32), sA, (T*)factors + (size_t)q0 * fs, status + q0, st, io32,
+                                     advio(a.w, (size_t)q0 * sw, io32), sw);
         });
     }
     a.fac = (T*)factors; a.fac_stride = fac_layout(n, m, q, a.images).total; a.status = status;
@@ -140,7 +143,7 @@ int api_pre_factor(int B, int n, int m, int q, const void* Q, int64_t sQ, const 
             const int nbn = tile_nb(n + q);
             const size_t pb = lds_elems_prefac_tile(nbn, (m + 15) / 16) * sizeof(double);
             prefac_deal(nbn, n + q, m, a.pf_k, a.pf_r);
-#define QPX_PICK(NBN, EQ) if (nbn == NBN && (q > 0) == EQ) return launch_prefac_tile<NBN, EQ>(a, pb, stream);
+#define QPX_PICK(NBN, EQ) if (nbn == NBN && (q > 0) == EQ) return a.w ? launch_prefac_tile<NBN + kPrefacSoft, EQ>(a, pb, stream) : launch_prefac_tile<NBN, EQ>(a, pb, stream);
             QPX_FORMS_PREFAC_TILE(QPX_PICK)         // (prefac_tile_serves: one of them matches)
 #undef QPX_PICK
         }
@@ -148,7 +151,7 @@ int api_pre_factor(int B, int n, int m, int q, const void* Q, int64_t sQ, const 
     if (use_grid(n, m, q)) {
         const int nba = sweep_nb(n + q + m);
         const size_t gb = lds_elems_sweep(nba) * sizeof(T);
-#define QPX_PICK(NBL) if (nba == NBL) return launch_sweep<T, NBL>(a, gb, stream);
+#define QPX_PICK(NBL) if (nba == NBL) return a.w ? launch_sweep<T, NBL + kPrefacSoft>(a, gb, stream) : launch_sweep<T, NBL>(a, gb, stream);
         QPX_FORMS_SWEEP(QPX_PICK)
 #undef QPX_PICK
     }
@@ -520,15 +523,23 @@ int qpx_can_share_factors(int dtype, int n, int m, int q)
     return qpx::use_big(n, m, q, dtype != QPX_F32 ? 8 : 4) ? 0 : 1;
 }
 
+int qpx_pre_factor_soft(int dtype, int B, int n, int m, int q, const void* Q, int64_t sQ, const void* G,
+                        int64_t sG, const void* A, int64_t sA, const void* w, int64_t sw, void* factors,
+                        int32_t* status, qpx_stream_t stream)
+{
+    const int e = qpx::check_dims(dtype, B, n, m, q);
+    if (e) return e;
+    if (sw < 0) return QPX_ERR_ARG;
+    return dtype != QPX_F32
+               ? qpx::api_pre_factor<double>(B, n, m, q, Q, sQ, G, sG, A, sA, factors, status, stream, dtype == QPX_F32_WIDE, w, sw)
+               : qpx::api_pre_factor<float>(B, n, m, q, Q, sQ, G, sG, A, sA, factors, status, stream, 0, w, sw);
+}
+
 int qpx_pre_factor(int dtype, int B, int n, int m, int q, const void* Q, int64_t sQ, const void* G,
                    int64_t sG, const void* A, int64_t sA, void* factors, int32_t* status,
                    qpx_stream_t stream)
 {
-    const int e = qpx::check_dims(dtype, B, n, m, q);
-    if (e) return e;
-    return dtype != QPX_F32
-               ? qpx::api_pre_factor<double>(B, n, m, q, Q, sQ, G, sG, A, sA, factors, status, stream, dtype == QPX_F32_WIDE)
-               : qpx::api_pre_factor<float>(B, n, m, q, Q, sQ, G, sG, A, sA, factors, status, stream);
+    return qpx_pre_factor_soft(dtype, B, n, m, q, Q, sQ, G, sG, A, sA, nullptr, 0, factors, status, stream);
 }
 
 int qpx_warm_supported(int dtype, int n, int m, int q)

@@ -1196,6 +1196,9 @@ template <class T, int NS> QPX_DEV void big_phase_body(const Block& b, const Big
 // op 1: y[0] = || x[0..len) ||_2 (one wave);
 // op 2: start of a pre-factorisation: zero the QP's control words, vONE = 1 on [0, m), 0 on the pad; vPQ = 0 on
 //       [0, q), 1 on the pad (the diagonal of S11 = Yt Yt^T there)
+// op 3: soft rows (qpx_pre_factor_soft), behind big_gemm_r: R_ii += w_i for the rows i < m (the padded diagonal keeps its
+//       value), a negative or non-finite entry of w into the QP's failure bits.  With `w` set, op 1 adds the number of
+//       soft rows (w_i > 0, i < m) under the root: || G'^T 1 ||, G' = [G, -E]
 template <class T> struct BigVecArgs {
     int B, op, len, n, m;
     T* fac; size_t fac_stride;
@@ -1203,6 +1206,7 @@ template <class T> struct BigVecArgs {
     T* y; size_t sy;
     T alpha, beta;
     int q, out32;
+    const T* w = nullptr; long long sw = 0; int w32 = 0;      // soft rows: w (B,m), float32 under w32 (QPX_F32_WIDE), sw = 0: shared
 };
 template <class T> QPX_DEV void big_vec_body(const Block& b, const BigVecArgs<T>& a, int qp)
 {
@@ -1216,7 +1220,21 @@ template <class T> QPX_DEV void big_vec_body(const Block& b, const BigVecArgs<T>
             T acc = T(0);
             for (int i = b.lane(); i < a.len; i += kWave) acc = fma_(x[i], x[i], acc);
             acc = wave_sum(b, acc);
+            if (a.w) acc += soft_rows(b, In<T>(a.w, (size_t)qp * a.sw, a.w32), a.m);
             if (b.lane() == 0) (a.y + (size_t)qp * a.sy)[0] = sqrt_(acc);
+        }
+    } else if (a.op == 3) {
+        const BigLayout L = big_layout(a.n, a.m, a.q);
+        T* F = a.fac + (size_t)qp * a.fac_stride;
+        const In<T> wg(a.w, (size_t)qp * a.sw, a.w32);
+        if (b.wave() == 0) {
+            bool bad = false;
+            for (int i = b.lane(); i < a.m; i += kWave) {
+                const T w = wg[i];
+                if (!(w >= T(0)) || !finite_(w)) bad = true;
+                else if (w > T(0)) F[L.R + big_at(L.MP, i, i)] += w;
+            }
+            if (b.any(bad) && b.lane() == 0) reinterpret_cast<int*>(F + L.ctrl)[bcFail] |= QPX_ST_NONFINITE;
         }
     } else {
         const BigLayout L = big_layout(a.n, a.m, a.q);

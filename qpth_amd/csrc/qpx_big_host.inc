@@ -266,7 +266,7 @@ int big_trsm_right_lt(const BigCtx<T>& c, size_t x, int nrb, size_t mat, size_t 
 
 template <class T>
 int big_pre_factor(int B, int n, int m, int q, const T* Q, int64_t sQ, const T* G, int64_t sG, const T* A, int64_t sA, T* fac,
-                   int32_t* status, void* stream, int io32)
+                   int32_t* status, void* stream, int io32, const T* w = nullptr, int64_t sw = 0)
 {
     BigCtx<T> c{B, n, m, fac, big_layout(n, m, q).total, big_layout(n, m, q), stream, q};
     const BigLayout& L = c.L;
@@ -292,6 +292,7 @@ int big_pre_factor(int B, int n, int m, int q, const T* Q, int64_t sQ, const T* 
     if ((e = big_mv<T>(c, L.Zt, L.NP, m, n, 1, L.v(bvONE), 0, false, L.v(bvY), T(1), T(0), 0))) return e;
     v = BigVecArgs<T>{};
     v.B = B; v.op = 1; v.len = n; v.x = fac + L.v(bvY); v.sx = c.fs; v.y = fac + L.scal + bsGt1; v.sy = c.fs;
+    v.m = m; v.w = w; v.sw = sw; v.w32 = io32;                 // soft rows: + their number under the root
     if ((e = launch_big_vec<T>(v, stream))) return e;
     // [Zt; Yt] = [G; A] Lq^-T: one pass over the stacked rows (Yt lies right behind Zt with the same row length)
     if ((e = big_trsm_right_lt<T>(c, L.Zt, nbm + nbe, L.Lq, L.Wq, nbq))) return e;
@@ -319,6 +320,11 @@ int big_pre_factor(int B, int n, int m, int q, const T* Q, int64_t sQ, const T* 
         if ((e = big_mm<T>(c, Zt, 0, 0, nbm, nbq, Us, 0, 0, Yt, 0, 0, nbe, T(-1), false, 0, 0, 1))) return e;
     }
     if ((e = big_gemm_r<T>(B, n, m, fac, stream, q))) return e;
+    if (w) {                                                   // soft rows: R + diag(w)
+        v = BigVecArgs<T>{};
+        v.B = B; v.op = 3; v.n = n; v.m = m; v.q = q; v.fac = fac; v.fac_stride = c.fs; v.w = w; v.sw = sw; v.w32 = io32;
+        if ((e = launch_big_vec<T>(v, stream))) return e;
+    }
     // status words: the pre-factorisation's failure bits
     BigPhaseArgs<T> ph{};
     ph.B = B; ph.n = n; ph.m = m; ph.q = q; ph.phase = 6; ph.fac = fac; ph.fac_stride = c.fs; ph.status = status;

@@ -30,6 +30,11 @@ constexpr int kKktMultiRole = 64;
 // workgroup of a CU.  qpth_amd/kkt.py: MULTI_RHS_BLOCK.
 constexpr int kKktMultiRB = 4;
 
+// Every pre-factorisation form exists a second time for soft rows (qpx_pre_factor_soft): blocks / tile rows + kPrefacSoft in
+// the form's FIRST parameter, as above (sweep_body / prefac_tile_body decode it).  The hard forms hold none of the soft
+// rows' code: their registers are the ones they had without it.
+constexpr int kPrefacSoft = 64;
+
 }  // namespace qpx
 
 // thread-grid kernels: (blocks of 16 -- of 8 in the one-wave grid -- per side), (blocks, slots of 64 columns)

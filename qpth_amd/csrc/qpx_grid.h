@@ -650,9 +650,11 @@ template <class T, int NBL> struct SweepBlocks<T, NBL, NBL> {
 //       [  M,   W,    -R ]]      K = Q^-1 - Q^-1 A^T S11^-1 A Q^-1,  N = Q^-1 A^T S11^-1,
 //                                M = G K,  W = G N,  R = G K G^T  (the reference's R)
 // i.e. everything forward and backward need, with no triangular solve anywhere.
-template <class T, int NBL>
+template <class T, int NBLF>          // NBLF: blocks of 16 of the augmented order (+ kPrefacSoft: the form for soft rows, a.w set)
 QPX_DEV void sweep_body(const Block& blk, const PrefactorArgs<T>& a, int qp, T* lds)
 {
+    constexpr bool kSoft = NBLF >= kPrefacSoft;
+    constexpr int NBL = kSoft ? NBLF - kPrefacSoft : NBLF;
     constexpr int GS = 16, NT = 256, MA = GS * NBL;
     const GridPos<GS> g(blk);
     const int n = a.n, m = a.m, q = a.q, nq = n + q, na = n + q + m;
@@ -701,6 +703,7 @@ QPX_DEV void sweep_body(const Block& blk, const PrefactorArgs<T>& a, int qp, T* 
             for (int j = blk.lane(); j < n; j += kWave) acc = fma_(vout[j], vout[j], acc);
             acc = wave_sum(blk, acc);
             if (blk.lane() == 0) F[lay.scal] = sqrt_(acc);
+            if (kSoft && blk.lane() == 0) vout[MA - 1] = acc;      // for the soft rows at the end of the kernel (nothing below touches vout)
         }
     }
     QPX_PROF(1)
@@ -773,6 +776,13 @@ QPX_DEV void sweep_body(const Block& blk, const PrefactorArgs<T>& a, int qp, T* 
         QPX_PROF_DUMP(F + lay.prof, T)
     }
     if (blk.tid == 0) a.status[qp] = 0;
+    if constexpr (kSoft) {                                         // soft rows: R + diag(w), behind the stores above
+        GridPos<GS>::sync(blk);
+        if (blk.tid < kWave) {
+            const bool bad = soft_blob(blk, In<T>(a.w, (size_t)qp * a.sw, a.io32), m, F, lay, wRg, wRw, wRm, vout[MA - 1]);
+            if (bad && blk.tid == 0) a.status[qp] = QPX_ST_NONFINITE;
+        }
+    }
 }
 
 QPX_LAYOUT_HD size_t lds_elems_sweep(int nbl) { return (size_t)3 * 16 * nbl + 8 + (size_t)nbl * 256; }

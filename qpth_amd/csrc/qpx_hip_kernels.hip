@@ -61,7 +61,8 @@ template <class T, int NBL> int launch_sweep(const PrefactorArgs<T>& a, size_t l
 {
     return launch_kernel<k_sweep<T, NBL>>(dim3(a.B), 256, lds_bytes, stream, a);
 }
-#define QPX_INST(NBL) template int launch_sweep<QPX_TU_REAL, NBL>(const PrefactorArgs<QPX_TU_REAL>&, size_t, void*);
+#define QPX_INST(NBL) template int launch_sweep<QPX_TU_REAL, NBL>(const PrefactorArgs<QPX_TU_REAL>&, size_t, void*); \
+                      template int launch_sweep<QPX_TU_REAL, NBL + kPrefacSoft>(const PrefactorArgs<QPX_TU_REAL>&, size_t, void*);      // (and its form for soft rows)
 QPX_FORMS_SWEEP(QPX_INST)
 #elif QPX_TU_KERNEL == 6
 // two workgroups per CU (2 waves per SIMD) for the common sizes: the two QPs hide each other's
@@ -147,7 +148,8 @@ template <int NBN, bool kEq> int launch_prefac_tile(const PrefactorArgs<double>&
 {
     return launch_kernel<k_prefac_tile<NBN, kEq>>(dim3(a.B), 256, lds_bytes, stream, a);
 }
-#define QPX_INST(NBN, EQ) template int launch_prefac_tile<NBN, EQ>(const PrefactorArgs<double>&, size_t, void*);
+#define QPX_INST(NBN, EQ) template int launch_prefac_tile<NBN, EQ>(const PrefactorArgs<double>&, size_t, void*); \
+                          template int launch_prefac_tile<NBN + kPrefacSoft, EQ>(const PrefactorArgs<double>&, size_t, void*);       // (and its form for soft rows)
 QPX_FORMS_PREFAC_TILE(QPX_INST)
 #elif QPX_TU_KERNEL == 10 || QPX_TU_KERNEL == 11
 // defined below, outside the launcher chain

@@ -99,6 +99,38 @@ template <class T> QPX_DEV void put_(T* base, int io32, size_t i, T v)
 }
 
 // ------------------------------------------------------------------------------------------
+// Soft rows (qpx_pre_factor_soft): w (m), w_i = 1 / rho_i > 0 on a soft row, 0 on a hard one.  The blob of the
+// softened QP is the hard one's with R_ii + w_i on the diagonal of R and the number of soft rows under the root of
+// || G^T 1 ||.  soft_rows is the large-QP family's; the thread-grid / tile pre-factorisations call soft_blob at their very
+// end, behind a block-uniform `if (a.w)`: by ONE wave, `acc` = || G^T 1 ||^2 as the kernel summed it (handed on in LDS).
+template <class T> QPX_DEV T soft_rows(const Block& b, const In<T>& wg, int m)
+{
+    T cnt = T(0);
+    for (int i = b.lane(); i < m; i += kWave) cnt += (wg[i] > T(0)) ? T(1) : T(0);
+    return wave_sum(b, cnt);
+}
+// the diagonal of every image of R the blob holds (rows < m: the padding keeps its diagonal) and the scalar; true in every
+// lane where an entry of w is negative or not finite (such an entry adds nothing)
+template <class T> QPX_DEV bool soft_blob(const Block& b, const In<T>& wg, int m, T* F, const FacLayout& lay, bool wRg, bool wRw, bool wRm, T acc)
+{
+    bool bad = false;
+    T cnt = T(0);
+    for (int i = b.lane(); i < m; i += kWave) {
+        const T w = wg[i];
+        if (!(w >= T(0)) || !finite_(w)) bad = true;
+        else if (w > T(0)) {
+            cnt += T(1);
+            if (wRg) F[lay.Rg + (size_t)(tri(i >> 4) + (i >> 4)) * 256 + (size_t)(17 * (i & 15))] += w;
+            if (wRw) F[lay.Rw + (size_t)(tri(i >> 3) + (i >> 3)) * 64 + (size_t)(9 * (i & 7))] += w;
+            if (wRm) F[lay.Rm + tile_image_index(i, i)] += w;
+        }
+    }
+    cnt = wave_sum(b, cnt);
+    if (b.lane() == 0) F[lay.scal] = sqrt_(acc + cnt);          // || G'^T 1 ||, G' = [G, -E]
+    return b.any(bad);
+}
+
+// ------------------------------------------------------------------------------------------
 // kernel argument blocks (plain data, passed by value)
 
 template <class T> struct PrefactorArgs {
@@ -113,6 +145,9 @@ template <class T> struct PrefactorArgs {
     // matrix-core form (qpx_prefac.h) only: which tiles of K (pf_k) and of R (pf_r) each of the four waves computes, bit
     // t = tile (i, j), t = i (i + 1) / 2 + j -- a greedy balance the host works out once per launch (prefac_deal)
     unsigned pf_k[4] = {0, 0, 0, 0}, pf_r[4] = {0, 0, 0, 0};
+    // soft rows (qpx_pre_factor_soft): w (B,m), float32 under io32, batch stride sw (0 = shared); NULL = qpx_pre_factor
+    const T* w = nullptr;
+    long long sw = 0;
 };
 
 template <class T> struct IpmArgs {

@@ -88,8 +88,8 @@ inline void prefac_deal(int nbn, int n, int m, unsigned (&pf_k)[4], unsigned (&p
 //   [M^T; W^T] = V^T S Yt,   R = Yt^T S Yt
 // -- the products of the neq = 0 kernel with the rows n .. nn - 1 of one operand negated, and three more arrays of the
 // blob read off the rows beyond n of the results: -N^T and S11^-1 from the tiles of Ka^-1, W^T from the rows of M^T.
-template <int NBN, bool kEq = false>
-QPX_DEV void prefac_tile_body(const Block& b, const PrefactorArgs<double>& a, int qp, double* lds)
+template <int NBN, bool kEq, bool kSoft>       // kSoft: the form for soft rows (a.w set)
+QPX_DEV void prefac_tile_form(const Block& b, const PrefactorArgs<double>& a, int qp, double* lds)
 {
     using T = double;
     using TM = TileMat<NBN, 4, true>;
@@ -469,6 +469,7 @@ QPX_DEV void prefac_tile_body(const Block& b, const PrefactorArgs<double>& a, in
         }
         acc = wave_sum(b, acc);
         if (lane == 0) F[lay.scal] = sqrt_(acc);
+        if (kSoft && lane == 0) flag[1] = acc;                // for the soft rows at the end of the kernel
     }
     b.sync();
     QPX_PROF(6)
@@ -524,6 +525,20 @@ QPX_DEV void prefac_tile_body(const Block& b, const PrefactorArgs<double>& a, in
     QPX_PROF(7)
     QPX_PROF_DUMP(F + lay.prof, T)
     if (b.tid == 0) a.status[qp] = 0;
+    if constexpr (kSoft) {                                    // soft rows: R + diag(w), behind the tiles' stores
+        b.sync();
+        if (b.tid < kWave) {
+            const bool bad = soft_blob(b, In<T>(a.w, (size_t)qp * a.sw, a.io32), m, F, lay, false, false, true, flag[1]);
+            if (bad && b.tid == 0) a.status[qp] = QPX_ST_NONFINITE;
+        }
+    }
+}
+
+// NBNF: tile rows of nz + neq, + kPrefacSoft (qpx_forms.h) for the form that serves soft rows
+template <int NBNF, bool kEq = false>
+QPX_DEV void prefac_tile_body(const Block& b, const PrefactorArgs<double>& a, int qp, double* lds)
+{
+    prefac_tile_form<(NBNF >= kPrefacSoft ? NBNF - kPrefacSoft : NBNF), kEq, (NBNF >= kPrefacSoft)>(b, a, qp, lds);
 }
 
 }  // namespace qpx

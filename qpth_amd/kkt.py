@@ -92,6 +92,19 @@ def _is_shared(X, B):
     return X.dim() == 2 or X.stride(0) == 0 or (B > 1 and X.size(0) == 1)
 
 
+def as_rho(rho, Q, nineq, nBatch=1):
+    """The penalties of the soft rows as every entry point takes them: a tensor of Q's dtype and device, shape
+    (nBatch, nineq), (nineq,) or (), or a Python number (-> a 0-dim tensor).  Raises ValueError otherwise; the VALUES
+    (> 0, +inf = a hard row) are checked by the pre-factorisation kernel (KKTFactors.raise_on_failure)."""
+    if not torch.is_tensor(rho):
+        rho = torch.tensor(float(rho), dtype=Q.dtype, device=Q.device)
+    if rho.dtype != Q.dtype or rho.device != Q.device:
+        raise ValueError("qpth_amd: rho is %s on %s, the QP is %s on %s" % (rho.dtype, rho.device, Q.dtype, Q.device))
+    if rho.dim() > 2 or (rho.dim() >= 1 and rho.size(-1) != nineq) or (rho.dim() == 2 and nBatch > 1 and rho.size(0) != nBatch):
+        raise ValueError("qpth_amd: rho has shape %s; expected (nBatch, %d), (%d,) or ()" % (tuple(rho.shape), nineq, nineq))
+    return rho
+
+
 class _PinnedPool:
     """Pinned int32 host buffers for the one small D2H copy behind a pre-factorisation (the per-QP status words).  A buffer
     belongs to exactly ONE KKTFactors from `take` until that object has read it (raise_on_failure) or dies; only then can
@@ -150,11 +163,16 @@ _PINNED = _PinnedPool()
 
 class KKTFactors:
     @classmethod
-    def build(cls, Q, G, A, nBatch=None, wide=False):
+    def build(cls, Q, G, A, nBatch=None, wide=False, w=None):
         """pre_factor_kkt(Q, G, A)   (batch.py:375-429); enqueues one kernel, no host sync.
         wide: float32 tensors, float64 factors and arithmetic (QPX_F32_WIDE, include/qpx.h): every later call on these
-        factors takes and returns float32 tensors, the blob is float64."""
+        factors takes and returns float32 tensors, the blob is float64.
+        w (B, nineq), (1, nineq) or (nineq,), >= 0: soft rows -- the factors of the QP with the penalty 1/2 sum t_i^2 / w_i on
+        the violation of G z <= h + t, w_i = 0 a hard row (qpx_pre_factor_soft).  Every launch on soft factors
+        serves the softened QP; they have no refinement and no finishing stage (refine_ok, polish_ok are False: both
+        would evaluate residuals of the hard QP).  A w per QP beside Q, G, A the batch shares means one blob per QP."""
         self = cls()
+        self.soft = w is not None
         self.wide = bool(wide)
         if self.wide and Q.dtype != torch.float32:
             raise TypeError("qpth_amd: wide=True is for float32 tensors")
@@ -174,6 +192,12 @@ class KKTFactors:
                                    "dtype and one device)" % (what, X.dtype, X.device, Q.dtype, Q.device))
             if X.dim() not in (2, 3) or (X.dim() == 3 and X.size(0) not in (1, B)):
                 raise RuntimeError("qpth_amd: %s has shape %s for a batch of %d" % (what, tuple(X.shape), B))
+        if self.soft:
+            if w.dtype != Q.dtype or w.device != Q.device:
+                raise RuntimeError("qpth_amd: w (1 / rho) is %s on %s but Q is %s on %s" % (w.dtype, w.device, Q.dtype, Q.device))
+            if tuple(w.shape) not in ((self.m,), (1, self.m), (B, self.m)):
+                raise RuntimeError("qpth_amd: w (1 / rho) has shape %s, expected (%d, %d) or (%d,)" % (tuple(w.shape), B, self.m, self.m))
+            w = w.detach()
         self.lib = _lib.backend_for(Q)
         self.dtype, self.device = Q.dtype, Q.device
         self.Q, self.G, self.A = Q, G, (A if self.q else None)     # the original data: iterative refinement evaluates residuals with it
@@ -193,13 +217,20 @@ class KKTFactors:
                           and bool(self.lib.dll.qpx_polish_supported(pcode, self.n, self.m, self.q)))
         share_ok = bool(self.lib.dll.qpx_can_share_factors(code, self.n, self.m, self.q))
         self.shared = B > 1 and share_ok and _is_shared(Q, B) and _is_shared(G, B) and _is_shared(A, B)
+        if self.soft:
+            self.refine_ok = self.polish_ok = False
+            w_shared = w.dim() == 1 or w.stride(0) == 0 or (B > 1 and w.size(0) == 1)
+            self.shared = self.shared and w_shared
+            if not self.shared and w_shared:
+                w = w.reshape(1, self.m)[:1].expand(B, self.m)      # per-QP blobs: the kernel reads it with batch stride 0
+        self.w = w
         nblob = 1 if self.shared else B
         self.sfac = 0 if self.shared else self.elems
         self.blob = torch.empty(nblob * self.elems, dtype=torch.float64 if self.wide else Q.dtype, device=Q.device)
         self.status = torch.empty(B, dtype=torch.int32, device=Q.device)      # every pre-factorisation kernel writes it
         with self._knob():
             self.lib.pre_factor(nblob, self.n, self.m, self.q, Q, G, A if self.q else None, self.blob, self.status,
-                                wide=self.wide)
+                                wide=self.wide, w=w)
         if self.shared:
             self.status[1:] = self.status[0]
         # The reference raises on a bad Q / A from inside forward (qp.py:81-85, batch.py:379-386).  The two
@@ -217,6 +248,9 @@ class KKTFactors:
                 self._pre_host.copy_(self.status[:nblob], non_blocking=True)
                 self._pre_event = torch.cuda.Event()
                 self._pre_event.record(torch.cuda.current_stream(self.device))
+        # soft rows: a bad entry of w is the pre-factorisation's QPX_ST_NONFINITE, a bit the loop may set too -- where no
+        # pinned copy holds the words as the pre-factorisation left them, a copy on the device does
+        self._pre_soft = self.status[:nblob].clone() if (self.soft and self._pre_event is None) else None
         return self
 
     def _release_pinned(self, done):
@@ -250,7 +284,11 @@ class KKTFactors:
     # -- error surface of pre_factor_kkt / QPFunction (qp.py:81-85, batch.py:379-386) ------
     def raise_on_failure(self, check_Q_spd=False):
         mask = _lib.ST_Q_NOT_SPD | _lib.ST_A_RANK
-        if self._pre_event is not None:
+        if self.soft:
+            mask |= _lib.ST_NONFINITE
+        if self._pre_soft is not None:
+            st = int(np.bitwise_or.reduce(self._pre_soft.cpu().numpy().reshape(-1))) & mask
+        elif self._pre_event is not None:
             if self._pre_bits is None:         # first reading: wait for the copy, keep the bits, free the buffer
                 self._pre_event.synchronize()
                 self._pre_bits = int(np.bitwise_or.reduce(self._pre_host.numpy()))
@@ -269,6 +307,14 @@ a non-zero diagonal.
         if st & _lib.ST_A_RANK:
             raise RuntimeError("qpth_amd Error: A Q^-1 A^T is not positive definite; "
                                "the equality constraints must have full row rank.")
+        if st & _lib.ST_NONFINITE:
+            raise ValueError("rho must be positive")
+
+    def _no_refine_on_soft(self, refine, what):
+        """refinement evaluates residuals from the caller's Q, G, A: of the HARD QP"""
+        if self.soft and refine > 0:
+            raise ValueError("qpth_amd: %s with refine=%d on factors with soft rows (w / rho): in-kernel refinement evaluates the "
+                             "residuals of the hard QP; pass refine=0" % (what, refine))
 
     def _check(self, X, k, what, batched_ok=True):
         """The kernels index raw pointers: a tensor of another dtype, device or shape must never reach them (the
@@ -343,6 +389,7 @@ a non-zero diagonal.
     def solve_kkt(self, d, rx, rs, rz, ry, refine=0):
         """factor_kkt + solve_kkt; refine > 0: that many steps of iterative refinement on the residual of the original
         KKT system (batch.py:228-270, KKTSolvers.IR_UNOPT) inside the kernel, re-using the factorisation."""
+        self._no_refine_on_soft(refine, "solve_kkt")
         B, n, m, q = self.B, self.n, self.m, self.q
         dt, dev = self.dtype, self.device
         d = self._vec(d, m, "d")
@@ -373,6 +420,7 @@ a non-zero diagonal.
         One launch and one factorisation of T = R + diag(1/d) per QP (qpx_factor_solve_kkt_multi) where the thread-grid /
         tile kernels serve the size and refine == 0.  Otherwise -- the large-QP family (nz+neq+nineq > 208), refine > 0 --
         the same result costs K launches of solve_kkt on slices, each with a factorisation of its own.  No host sync."""
+        self._no_refine_on_soft(refine, "solve_kkt_many")
         B, n, m, q = self.B, self.n, self.m, self.q
         dt, dev = self.dtype, self.device
         given = [X for X in (rx, rs, rz, ry if q else None) if X is not None and X.nelement() > 0]
@@ -416,6 +464,9 @@ a non-zero diagonal.
         / tile kernels serve the size, a stream-ordered sequence of the large-QP family's launches beyond (v7).  No host
         sync.  (Rounds 2-4 composed this stage from torch operations on the host side for the sizes without a kernel;
         that version now lives in tests/polish_reference.py as the step-by-step reference of the kernels.)"""
+        if self.soft:
+            raise ValueError("qpth_amd: no finishing stage (qpx_polish: KKTSolvers.IR_UNOPT, float32 refine=k) on factors with "
+                             "soft rows (w / rho): its steps evaluate the residuals of the hard QP")
         if self.polish_ok:
             B, n, m, q = self.B, self.n, self.m, self.q
             self._check(p, n, "p")
@@ -447,6 +498,7 @@ a non-zero diagonal.
         parameter's shape, batched, batch-1 or shared -- at the forward's (zhat, lam, slacks, nu): ONE KKT solve with the
         matrix the backward factors (d = clamp(lam) / clamp(slacks), qp.py:148), its right-hand side formed from the tangents
         inside the kernel (qpx_jvp, include/qpx.h).  Returns z' (B, n); want_duals: (z', lam', nu').  No host sync."""
+        self._no_refine_on_soft(refine, "jvp")
         B, n, m, q = self.B, self.n, self.m, self.q
         dt, dev = self.dtype, self.device
         ts = []
@@ -472,14 +524,17 @@ a non-zero diagonal.
 
     # -- QPFunctionFn.backward (qp.py:127-182) ------------------------------------------------
     def backward(self, zhat, lam, slacks, nu, dl_dz, want=(True,) * 6, shared=(False,) * 6, refine=0,
-                 dl_dlam=None, dl_dnu=None):
+                 dl_dlam=None, dl_dnu=None, want_dz=False):
         """Gradients (dQ, dp, dG, dh, dA, db) for the parameters `want` asks for (ctx.needs_input_grad;
         the others come back as None and cost nothing).  A parameter flagged in `shared` is one the whole
         batch shares: its gradient is returned already reduced to the reference's `.mean(0)` (qp.py:159-177)
         -- for the matrices by one contraction over the batch (qpx_batch_outer) instead of B outer products.
         dl_dlam (B, m), dl_dnu (B, q): cotangents of the multipliers lam*, nu* (None = zero; dl_dz may then be None too,
         but not all three): the same launch with the right-hand side (dl_dz, 0, dl_dlam, dl_dnu) -- qpx_backward_duals,
-        the exact adjoint of jvp(..., want_duals=True)."""
+        the exact adjoint of jvp(..., want_duals=True).
+        want_dz: a seventh value behind the six, dz (B, m) of the KKT solution as the launch wrote it -- the gradient with
+        respect to the w of soft factors is -dz lam."""
+        self._no_refine_on_soft(refine, "backward")
         B, n, m, q = self.B, self.n, self.m, self.q
         dt, dev = self.dtype, self.device
         wQ, wp, wG, wh, wA, wb = [bool(w) for w in want]
@@ -500,7 +555,7 @@ a non-zero diagonal.
         dh = buf(wh and not sh, B, m)
         db = buf(wb and not sb, B, q)
         dx = buf((wp and sp) or (wQ and sQ) or (wG and sG) or (wA and sA), B, n)
-        dz = buf((wh and sh) or (wG and sG), B, m)
+        dz = buf((wh and sh) or (wG and sG) or want_dz, B, m)
         dy = buf(q > 0 and ((wb and sb) or (wA and sA)), B, q)
         zh, lm, nv = self._vec(zhat, n, "zhat"), self._vec(lam, m, "lam"), self._vec(nu, q, "nu")
         gz, gl, gn = self._vec(dl_dz, n, "dl_dz"), self._vec(dl_dlam, m, "dl_dlam"), self._vec(dl_dnu, q, "dl_dnu")
@@ -532,4 +587,6 @@ a non-zero diagonal.
             if wb and sb:
                 db = torch.empty(q, dtype=dt, device=dev)
                 self.lib.batch_outer(dy, None, None, None, -1.0, db)
+        if want_dz:
+            return dQ, dp, dG, dh, dA, db, dz
         return dQ, dp, dG, dh, dA, db

@@ -12,6 +12,7 @@ Forward mode (torch.autograd.forward_ad, which the reference does not support) i
 the backward's KKT system with the right-hand side formed from the input tangents (qpx_jvp).
 QPFunction(duals=True) also returns the multipliers, differentiable in both modes: (zhat, nu, lam, slacks).
 QPFunction(warm_start=ws) starts the loop at the previous call's (lam, slacks) kept in a qpth_amd.WarmStart.
+QPFunction(...)(Q, p, G, h, A, b, rho) softens rows of G z <= h by a quadratic penalty, differentiable in rho too.
 """
 from enum import Enum
 
@@ -19,7 +20,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib
-from .kkt import KKTFactors
+from .kkt import KKTFactors, as_rho
 from .solvers.pdipm import batch as pdipm_b
 from .util import expandParam, extract_nBatch
 
@@ -53,7 +54,17 @@ def f64_arithmetic_serves(nz, nineq, neq, lib=None):
 def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                maxIter=20, solver=QPSolvers.PDIPM_BATCHED,
                check_Q_spd=True, refine=None, duals=False, warm_start=None):
-    """`refine`, `duals` and `warm_start` are the arguments the reference does not have.
+    """Returns f(Q, p, G, h, A, b, rho=None).  `refine`, `duals`, `warm_start` and the seventh input `rho` are what the reference
+    does not have.
+    rho: soft inequality rows,
+          min 1/2 z'Qz + p'z + 1/2 sum_i rho_i t_i^2   s.t.  Gz <= h + t,  Az = b,
+      solved in the kernels of the hard QP of the same (nz, nineq, neq) -- no augmented variables.  A tensor of the other
+      inputs' dtype and device, shape (nBatch, nineq), (nineq,) (shared by the batch) or () (one penalty for every row), or
+      a Python float; every entry > 0, +inf = a hard row.  A seventh differentiable input, in reverse and in forward mode;
+      a shared rho gets the `.mean(0)` convention of the other shared parameters, a scalar is summed over the rows as
+      well.  The violation is t = lam / rho, the returned slacks are h + t - G zhat.  Not with solver=QPSolvers.CVXPY and
+      not with refine > 0 (both raise ValueError); a rho <= 0 or NaN raises ValueError("rho must be positive") from the
+      forward.  rho=None is the hard QP, the six-input node as before.
     warm_start: a qpth_amd.WarmStart, the SAME object on every step of a training loop.  The first call is cold (the holder
       is empty); every later call enters the PDIPM loop at the previous call's (lam, slacks), floored at `ws.floor`, instead
       of the reference's start point, and needs about half the iterations while the parameters move by small steps (DESIGN
@@ -84,122 +95,193 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
     Memory: with refine=None a float32 batch in the large-QP family keeps a float64 factor blob (9.4 MB per QP at
     nz = nineq = 500, twice the float32 family's); a batch that only fits HBM with float32 factors should pass refine=2
     (float32 kernels + finishing iterations) or refine=0 explicitly."""
+    def _forward(ctx, Q_, p_, G_, h_, A_, b_, rho_=None):
+        nBatch = extract_nBatch(Q_, p_, G_, h_, A_, b_)
+        if rho_ is not None and rho_.dim() == 2:
+            nBatch = max(nBatch, rho_.size(0))
+        nineq, nz = G_.size(-2), G_.size(-1)
+        neq = A_.size(-2) if A_.nelement() > 0 else 0
+        # float32 data, float64 arithmetic (see QPFunction.__doc__)
+        ctx.wide = (solver == QPSolvers.PDIPM_BATCHED and refine is None and Q_.dtype == torch.float32
+                    and f64_arithmetic_serves(nz, nineq, neq, _lib.backend_for(Q_)))
+        Q, _ = expandParam(Q_, nBatch, 3)
+        p, _ = expandParam(p_, nBatch, 2)
+        G, _ = expandParam(G_, nBatch, 3)
+        h, _ = expandParam(h_, nBatch, 2)
+        A, _ = expandParam(A_, nBatch, 3)
+        b, _ = expandParam(b_, nBatch, 2)
+
+        assert(neq > 0 or nineq > 0)
+        ctx.neq, ctx.nineq, ctx.nz = neq, nineq, nz
+
+        if rho_ is not None:
+            # soft rows: w = 1 / rho (0 = hard, rho = inf) into the pre-factorisation; ctx keeps rho as (nBatch | 1, nineq)
+            if Q_.dtype == torch.float32 and refine is None and not ctx.wide:
+                raise ValueError("qpth_amd: rho with float32 inputs at nz = %d, nineq = %d, neq = %d, where the float32 "
+                                 "kernels would run with finishing steps on the residuals of the hard QP; pass refine=0 "
+                                 "(or float64 inputs)" % (nz, nineq, neq))
+            ctx.rho = rho_.detach().expand(nineq).unsqueeze(0) if rho_.dim() < 2 else rho_.detach()
+            w = ctx.rho.reciprocal()
+        else:
+            w = None
+
+        if solver == QPSolvers.PDIPM_BATCHED:
+            fac = KKTFactors.build(Q, G, A, nBatch, wide=ctx.wide, w=w)   # qp.py:93
+            warm = warm_start.pair(nBatch, nineq, Q.dtype, Q.device) if warm_start is not None else None
+            res = fac.ipm(p, h, b, eps, maxIter, notImprovedLim,
+                          want_trace=(verbose == 1), warm=warm,
+                          warm_floor=warm_start.floor if warm is not None else 1e-2)   # qp.py:94-96
+            ctx.refine = (2 if Q.dtype == torch.float32 and not ctx.wide else 0) if refine is None else int(refine)
+            if ctx.refine > 0:
+                # (the solves inside a finishing step are NOT refined: the step's own residuals are exact, and refining
+                # the directions as well changes nothing in the answer -- C2 / C3 float32, two steps: the same error
+                # distribution to three digits -- for 40 % more time per step; profiles/archive/r04f)
+                res = fac.polish(p, h, b, res, steps=ctx.refine, refine=0)
+            if warm_start is not None:
+                warm_start.take(res)
+            # one small read-back: the reference raises here too (qp.py:81-85, batch.py:379-386)
+            fac.raise_on_failure(check_Q_spd)
+            if verbose == 1:
+                _print_trace(res)
+            if verbose >= 0:
+                if not bool((res.best_resid <= 1.).all().item()):
+                    print(pdipm_b.INACC_ERR)                     # batch.py:141-142,205-206
+            ctx.fac = fac
+            zhats, ctx.nus, ctx.lams, ctx.slacks = res.zhat, res.nu, res.lam, res.slacks
+        elif solver == QPSolvers.CVXPY:
+            # forward by an external CPU solver, backward by the HIP kernels (qp.py:97-120,142-143)
+            from .solvers import external
+            zhats, ctx.nus, ctx.lams, ctx.slacks = external.forward_batch(Q, p, G, h, A, b, neq)
+            ctx.fac = None
+            ctx.refine = 0 if refine is None else int(refine)
+        else:
+            assert False
+
+        # (rho among the saved tensors: backward reads it there, under autograd's check for in-place changes; forward mode,
+        # which runs inside this very call, reads ctx.rho)
+        ctx.save_for_backward(zhats, Q_, p_, G_, h_, A_, b_, *(() if rho_ is None else (rho_,)))
+        ctx.rho_dim = None if rho_ is None else rho_.dim()
+        # forward mode reads no saved_tensors: zhat as an attribute beside lam, s, nu (detached: no cycle through the
+        # output's grad_fn), and on the external-solver path the matrices the factors are rebuilt from
+        ctx.zhat = zhats.detach()
+        ctx.QGA = (Q.detach(), G.detach(), A.detach(), nBatch) if ctx.fac is None else None
+        if not duals:
+            return zhats
+        # the multipliers as outputs: ctx keeps detached aliases (no cycle through the outputs' grad_fn), and an output
+        # the loss does not use hands backward None instead of a tensor of zeros
+        nus, lams, slacks = ctx.nus, ctx.lams, ctx.slacks
+        ctx.nus, ctx.lams, ctx.slacks = nus.detach(), lams.detach(), slacks.detach()
+        ctx.set_materialize_grads(False)
+        if neq == 0:
+            ctx.mark_non_differentiable(slacks, nus)
+        else:
+            ctx.mark_non_differentiable(slacks)
+        return zhats, nus, lams, slacks
+
+    def _jvp(ctx, dQ, dp, dG, dh, dA, db, drho=None):
+        # forward mode: z' solves the backward's KKT system (same d, same factors) with the right-hand side formed from
+        # the tangents on the device -- one launch, no host sync (DESIGN 4.4).  A None / empty tangent is zero.
+        fac = ctx.fac
+        if fac is None:                                          # external solver: the factors as backward builds them
+            Q, G, A, nBatch = ctx.QGA
+            fac = KKTFactors.build(Q, G, A, nBatch)
+            fac.raise_on_failure(check_Q_spd)
+        rf = 1 if (ctx.refine > 0 and fac.refine_ok) else 0
+        if drho is not None:
+            # w = 1 / rho enters the KKT rows like h times lam (G z - w lam + s = h): th + tw lam, tw = -trho / rho^2
+            tw = -drho / (ctx.rho * ctx.rho)
+            dh = tw * ctx.lams if dh is None else dh + tw * ctx.lams
+        if not duals:
+            return fac.jvp(ctx.zhat, ctx.lams, ctx.slacks, ctx.nus, (dQ, dp, dG, dh, dA, db), refine=rf)
+        # (z', nu', lam') from the same single launch; the slacks carry no tangent (non-differentiable)
+        zt, lt, nt = fac.jvp(ctx.zhat, ctx.lams, ctx.slacks, ctx.nus, (dQ, dp, dG, dh, dA, db), refine=rf, want_duals=True)
+        return zt, nt, lt, None
+
+    def _backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
+        zhats, Q, p, G, h, A, b = ctx.saved_tensors[:7]
+        nBatch = extract_nBatch(Q, p, G, h, A, b)
+        Q, Q_e = expandParam(Q, nBatch, 3)
+        p, p_e = expandParam(p, nBatch, 2)
+        G, G_e = expandParam(G, nBatch, 3)
+        h, h_e = expandParam(h, nBatch, 2)
+        A, A_e = expandParam(A, nBatch, 3)
+        b, b_e = expandParam(b, nBatch, 2)
+        neq = ctx.neq
+        soft = ctx.rho_dim is not None
+        if dl_dzhat is None and dl_dlam is None and (dl_dnu is None or neq == 0):
+            return (None,) * (7 if soft else 6)                  # duals=True and no cotangent on any differentiable output
+
+        fac = ctx.fac
+        if fac is None:                                          # qp.py:142-143
+            fac = KKTFactors.build(Q, G, A, nBatch)
+            fac.raise_on_failure(check_Q_spd)
+
+        # d = clamp(lams)/clamp(slacks), factor_kkt, solve_kkt(dl_dzhat, 0, 0, 0) -- with duals=True
+        # solve_kkt(dl_dzhat, 0, dl_dlam, dl_dnu), each None where the loss does not use that output -- and the outer
+        # products (qp.py:148-173) happen inside one kernel.  Only the gradients autograd asks for are
+        # formed (ctx.needs_input_grad), and the `.mean(0)` of a parameter the batch shares
+        # (qp.py:159-177) is taken inside KKTFactors.backward -- for Q, G, A as one contraction over
+        # the batch instead of nBatch outer products.
+        want = tuple(ctx.needs_input_grad[:6])
+        want_rho = soft and ctx.needs_input_grad[6]
+        grads = fac.backward(zhats, ctx.lams, ctx.slacks, ctx.nus, dl_dzhat, want=want,
+                             shared=(Q_e, p_e, G_e, h_e, A_e, b_e),
+                             refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0,
+                             dl_dlam=dl_dlam, dl_dnu=dl_dnu if neq > 0 else None, want_dz=want_rho)
+        if want_rho:
+            grads, dz = grads[:6], grads[6]
+        if neq == 0:
+            grads = grads[:4] + (None, None)
+        if not soft:
+            return grads
+        drho = None
+        if want_rho:
+            # dw = -dz lam, w = 1 / rho: drho = dz lam / rho^2 (0 on a hard row); shared: `.mean(0)`, a scalar summed over the rows
+            rho = ctx.saved_tensors[7]
+            rho = rho.expand(ctx.nineq).unsqueeze(0) if ctx.rho_dim < 2 else rho
+            drho = dz * ctx.lams / (rho * rho)
+            if ctx.rho_dim < 2:
+                drho = drho.mean(0)
+            if ctx.rho_dim == 0:
+                drho = drho.sum()
+        return grads + (drho,)
+
     class QPFunctionFn(Function):
         @staticmethod
         def forward(ctx, Q_, p_, G_, h_, A_, b_):
-            nBatch = extract_nBatch(Q_, p_, G_, h_, A_, b_)
-            nineq, nz = G_.size(-2), G_.size(-1)
-            neq = A_.size(-2) if A_.nelement() > 0 else 0
-            # float32 data, float64 arithmetic (see QPFunction.__doc__)
-            ctx.wide = (solver == QPSolvers.PDIPM_BATCHED and refine is None and Q_.dtype == torch.float32
-                        and f64_arithmetic_serves(nz, nineq, neq, _lib.backend_for(Q_)))
-            Q, _ = expandParam(Q_, nBatch, 3)
-            p, _ = expandParam(p_, nBatch, 2)
-            G, _ = expandParam(G_, nBatch, 3)
-            h, _ = expandParam(h_, nBatch, 2)
-            A, _ = expandParam(A_, nBatch, 3)
-            b, _ = expandParam(b_, nBatch, 2)
-
-            assert(neq > 0 or nineq > 0)
-            ctx.neq, ctx.nineq, ctx.nz = neq, nineq, nz
-
-            if solver == QPSolvers.PDIPM_BATCHED:
-                fac = KKTFactors.build(Q, G, A, nBatch, wide=ctx.wide)   # qp.py:93
-                warm = warm_start.pair(nBatch, nineq, Q.dtype, Q.device) if warm_start is not None else None
-                res = fac.ipm(p, h, b, eps, maxIter, notImprovedLim,
-                              want_trace=(verbose == 1), warm=warm,
-                              warm_floor=warm_start.floor if warm is not None else 1e-2)   # qp.py:94-96
-                ctx.refine = (2 if Q.dtype == torch.float32 and not ctx.wide else 0) if refine is None else int(refine)
-                if ctx.refine > 0:
-                    # (the solves inside a finishing step are NOT refined: the step's own residuals are exact, and refining
-                    # the directions as well changes nothing in the answer -- C2 / C3 float32, two steps: the same error
-                    # distribution to three digits -- for 40 % more time per step; profiles/archive/r04f)
-                    res = fac.polish(p, h, b, res, steps=ctx.refine, refine=0)
-                if warm_start is not None:
-                    warm_start.take(res)
-                # one small read-back: the reference raises here too (qp.py:81-85, batch.py:379-386)
-                fac.raise_on_failure(check_Q_spd)
-                if verbose == 1:
-                    _print_trace(res)
-                if verbose >= 0:
-                    if not bool((res.best_resid <= 1.).all().item()):
-                        print(pdipm_b.INACC_ERR)                     # batch.py:141-142,205-206
-                ctx.fac = fac
-                zhats, ctx.nus, ctx.lams, ctx.slacks = res.zhat, res.nu, res.lam, res.slacks
-            elif solver == QPSolvers.CVXPY:
-                # forward by an external CPU solver, backward by the HIP kernels (qp.py:97-120,142-143)
-                from .solvers import external
-                zhats, ctx.nus, ctx.lams, ctx.slacks = external.forward_batch(Q, p, G, h, A, b, neq)
-                ctx.fac = None
-                ctx.refine = 0 if refine is None else int(refine)
-            else:
-                assert False
-
-            ctx.save_for_backward(zhats, Q_, p_, G_, h_, A_, b_)
-            # forward mode reads no saved_tensors: zhat as an attribute beside lam, s, nu (detached: no cycle through the
-            # output's grad_fn), and on the external-solver path the matrices the factors are rebuilt from
-            ctx.zhat = zhats.detach()
-            ctx.QGA = (Q.detach(), G.detach(), A.detach(), nBatch) if ctx.fac is None else None
-            if not duals:
-                return zhats
-            # the multipliers as outputs: ctx keeps detached aliases (no cycle through the outputs' grad_fn), and an output
-            # the loss does not use hands backward None instead of a tensor of zeros
-            nus, lams, slacks = ctx.nus, ctx.lams, ctx.slacks
-            ctx.nus, ctx.lams, ctx.slacks = nus.detach(), lams.detach(), slacks.detach()
-            ctx.set_materialize_grads(False)
-            if neq == 0:
-                ctx.mark_non_differentiable(slacks, nus)
-            else:
-                ctx.mark_non_differentiable(slacks)
-            return zhats, nus, lams, slacks
+            return _forward(ctx, Q_, p_, G_, h_, A_, b_)
 
         @staticmethod
         def jvp(ctx, dQ, dp, dG, dh, dA, db):
-            # forward mode: z' solves the backward's KKT system (same d, same factors) with the right-hand side formed from
-            # the tangents on the device -- one launch, no host sync (DESIGN 4.4).  A None / empty tangent is zero.
-            fac = ctx.fac
-            if fac is None:                                          # external solver: the factors as backward builds them
-                Q, G, A, nBatch = ctx.QGA
-                fac = KKTFactors.build(Q, G, A, nBatch)
-                fac.raise_on_failure(check_Q_spd)
-            rf = 1 if (ctx.refine > 0 and fac.refine_ok) else 0
-            if not duals:
-                return fac.jvp(ctx.zhat, ctx.lams, ctx.slacks, ctx.nus, (dQ, dp, dG, dh, dA, db), refine=rf)
-            # (z', nu', lam') from the same single launch; the slacks carry no tangent (non-differentiable)
-            zt, lt, nt = fac.jvp(ctx.zhat, ctx.lams, ctx.slacks, ctx.nus, (dQ, dp, dG, dh, dA, db), refine=rf, want_duals=True)
-            return zt, nt, lt, None
+            return _jvp(ctx, dQ, dp, dG, dh, dA, db)
 
         @staticmethod
         def backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
-            zhats, Q, p, G, h, A, b = ctx.saved_tensors
-            nBatch = extract_nBatch(Q, p, G, h, A, b)
-            Q, Q_e = expandParam(Q, nBatch, 3)
-            p, p_e = expandParam(p, nBatch, 2)
-            G, G_e = expandParam(G, nBatch, 3)
-            h, h_e = expandParam(h, nBatch, 2)
-            A, A_e = expandParam(A, nBatch, 3)
-            b, b_e = expandParam(b, nBatch, 2)
-            neq = ctx.neq
-            if dl_dzhat is None and dl_dlam is None and (dl_dnu is None or neq == 0):
-                return (None,) * 6                                   # duals=True and no cotangent on any differentiable output
+            return _backward(ctx, dl_dzhat, dl_dnu, dl_dlam, dl_dslacks)
 
-            fac = ctx.fac
-            if fac is None:                                          # qp.py:142-143
-                fac = KKTFactors.build(Q, G, A, nBatch)
-                fac.raise_on_failure(check_Q_spd)
+    class QPSoftFunctionFn(Function):
+        """the seven-input node: rho, the penalties of the soft rows, behind the six parameters"""
+        @staticmethod
+        def forward(ctx, Q_, p_, G_, h_, A_, b_, rho_):
+            return _forward(ctx, Q_, p_, G_, h_, A_, b_, rho_)
 
-            # d = clamp(lams)/clamp(slacks), factor_kkt, solve_kkt(dl_dzhat, 0, 0, 0) -- with duals=True
-            # solve_kkt(dl_dzhat, 0, dl_dlam, dl_dnu), each None where the loss does not use that output -- and the outer
-            # products (qp.py:148-173) happen inside one kernel.  Only the gradients autograd asks for are
-            # formed (ctx.needs_input_grad), and the `.mean(0)` of a parameter the batch shares
-            # (qp.py:159-177) is taken inside KKTFactors.backward -- for Q, G, A as one contraction over
-            # the batch instead of nBatch outer products.
-            want = tuple(ctx.needs_input_grad[:6])
-            grads = fac.backward(zhats, ctx.lams, ctx.slacks, ctx.nus, dl_dzhat, want=want,
-                                 shared=(Q_e, p_e, G_e, h_e, A_e, b_e),
-                                 refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0,
-                                 dl_dlam=dl_dlam, dl_dnu=dl_dnu if neq > 0 else None)
-            if neq == 0:
-                grads = grads[:4] + (None, None)
-            return grads
-    return QPFunctionFn.apply
+        @staticmethod
+        def jvp(ctx, dQ, dp, dG, dh, dA, db, drho):
+            return _jvp(ctx, dQ, dp, dG, dh, dA, db, drho)
+
+        @staticmethod
+        def backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
+            return _backward(ctx, dl_dzhat, dl_dnu, dl_dlam, dl_dslacks)
+
+    def apply(Q, p, G, h, A, b, rho=None):
+        if rho is None:
+            return QPFunctionFn.apply(Q, p, G, h, A, b)
+        if solver != QPSolvers.PDIPM_BATCHED:
+            raise ValueError("qpth_amd: rho (soft inequality rows) is served by solver=QPSolvers.PDIPM_BATCHED only; with an "
+                             "external solver, augment the QP with the violations t as variables")
+        if refine is not None and int(refine) > 0:
+            raise ValueError("qpth_amd: rho with refine=%d: refinement and the finishing steps evaluate residuals of the hard "
+                             "QP; pass refine=0 (or refine=None with float64 inputs)" % int(refine))
+        rho = as_rho(rho, Q, G.size(-2), extract_nBatch(Q, p, G, h, A, b))
+        return QPSoftFunctionFn.apply(Q, p, G, h, A, b, rho)
+    return apply

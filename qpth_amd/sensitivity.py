@@ -15,7 +15,7 @@ An analysis interface, not an autograd node: every output is detached, and `QPFu
 import torch
 
 from . import _lib
-from .kkt import KKTFactors
+from .kkt import KKTFactors, as_rho
 from .qp import _print_trace, f64_arithmetic_serves
 from .solvers.pdipm import batch as pdipm_b
 from .util import expandParam, extract_nBatch
@@ -28,8 +28,9 @@ class QPSolution:
     """What the forward of QPFunction leaves behind: zhat (B,n), nu (B,q), lam, slacks (B,m), the factors (KKTFactors) and
     the parameters expanded to the batch (`params`: Q, p, G, h, A, b; `shared`: which of them the batch shares)."""
 
-    def __init__(self, fac, res, params, shared, refine):
+    def __init__(self, fac, res, params, shared, refine, rho=None, rho_dim=None):
         self.fac = fac
+        self.rho, self.rho_dim = rho, rho_dim       # soft rows (solve(rho=...)): rho as (B | 1, m) and the caller's rho.dim()
         self.zhat, self.nu, self.lam, self.slacks = res.zhat, res.nu, res.lam, res.slacks
         self.params = dict(zip(("Q", "p", "G", "h", "A", "b"), params))
         self.shared = dict(zip(("Q", "p", "G", "h", "A", "b"), shared))
@@ -41,14 +42,17 @@ class QPSolution:
         right-hand sides (dl_dz, 0, dl_dlam, dl_dnu), solved for all K in one launch (KKTFactors.solve_kkt_many).
         Returns a dict over `want` of K-stacked gradients: "p": dx (B,K,n), "h": -dz (B,K,m), "b": -dy (B,K,q), and the
         formulas of qpx_backward_duals for the matrices, "Q": 1/2 (dx zhat' + zhat dx') (B,K,n,n), "G": dz zhat' + lam dx'
-        (B,K,m,n), "A": dy zhat' + nu dx' (B,K,q,n).  The matrix gradients are composed on the host by torch.einsum and are
+        (B,K,m,n), "A": dy zhat' + nu dx' (B,K,q,n); after solve(rho=...), "rho": dz lam / rho^2 (B,K,m), 0 on a hard row
+        (a shared rho: the mean over B, (K,m); a scalar rho: summed over the rows too, (K,)).  The matrix gradients are composed on the host by torch.einsum and are
         bound by memory traffic: B K n n elements each -- 41 MB for "Q" in float64 at B = 512, K = n = 100, written once
         and, for a shared parameter, read again by the mean.  A parameter the batch shares gets the reference's `.mean(0)`
         over B (qp.py:159-177)."""
         fac, q = self.fac, self.fac.q
-        bad = [w for w in want if w not in _VECTORS + _MATRICES]
+        known = _VECTORS + _MATRICES + (("rho",) if self.rho is not None else ())
+        bad = [w for w in want if w not in known]
         if bad:
-            raise ValueError("qpth_amd: vjp_many: unknown parameter(s) %s; choose from %s" % (bad, _VECTORS + _MATRICES))
+            raise ValueError("qpth_amd: vjp_many: unknown parameter(s) %s; choose from %s%s"
+                             % (bad, known, "" if self.rho is not None else " ('rho' after solve(rho=...))"))
         if dl_dz is None and dl_dlam is None and (dl_dnu is None or q == 0):
             raise RuntimeError("qpth_amd: vjp_many needs at least one of dl_dz, dl_dlam, dl_dnu")
         d = torch.clamp(self.lam, min=1e-8) / torch.clamp(self.slacks, min=1e-8)            # qp.py:148
@@ -73,6 +77,11 @@ class QPSolution:
                 g = -dz
             elif w == "b":
                 g = -dy
+            elif w == "rho":
+                g = dz * (lam / (self.rho * self.rho)).unsqueeze(1)
+                g = (g if self.rho_dim == 2 else g.mean(0)) if self.rho_dim > 0 else g.mean(0).sum(-1)
+                out[w] = g.detach()
+                continue
             elif w == "Q":
                 g = 0.5 * (outer(dx, zh) + outer_t(zh, dx))
             elif w == "G":
@@ -85,7 +94,8 @@ class QPSolution:
     def jacobian(self, of=("z",), wrt=_VECTORS):
         """Jacobians of the solution -- and of the multipliers: `of` may add "lam" and "nu" -- with respect to the vector
         parameters in `wrt`, a dict keyed (of, wrt): J["z","p"] (B,n,n) with [b,i,j] = d zhat_i / d p_j, J["z","h"] (B,n,m),
-        J["z","b"] (B,n,q), J["lam","h"] (B,m,m), ...  vjp_many with identity cotangents: K = n (+ m + q) right-hand sides
+        J["z","b"] (B,n,q), J["lam","h"] (B,m,m), ...; after solve(rho=...) with a per-QP or shared vector rho, "rho" too:
+        J["z","rho"] (B,n,m).  vjp_many with identity cotangents: K = n (+ m + q) right-hand sides
         per QP, still one launch.  (The Jacobian with respect to a parameter the batch shares is the mean over the batch of
         the per-QP Jacobians, as vjp_many returns it.)"""
         fac = self.fac
@@ -93,8 +103,9 @@ class QPSolution:
         of = tuple(of)
         if not of or any(o not in ("z", "lam", "nu") for o in of):
             raise ValueError("qpth_amd: jacobian: `of` is a non-empty subset of ('z', 'lam', 'nu'), got %s" % (of,))
-        if any(w not in _VECTORS for w in wrt):
-            raise ValueError("qpth_amd: jacobian: only the vector parameters %s are allowed in `wrt`, got %s" % (_VECTORS, tuple(wrt)))
+        vectors = _VECTORS + (("rho",) if self.rho_dim is not None and self.rho_dim > 0 else ())
+        if any(w not in vectors for w in wrt):
+            raise ValueError("qpth_amd: jacobian: only the vector parameters %s are allowed in `wrt`, got %s" % (vectors, tuple(wrt)))
         sizes = {"z": n, "lam": m, "nu": q}
         rows, K = {}, 0
         for o in ("z", "lam", "nu"):
@@ -120,21 +131,34 @@ class QPSolution:
         return J
 
 
-def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd=True, verbose=-1, warm_start=None):
+def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd=True, verbose=-1, warm_start=None, rho=None):
     """The forward of QPFunction(eps, verbose, notImprovedLim, maxIter, check_Q_spd)(Q, p, G, h, A, b) with its defaults for
     float32 (float64 arithmetic where f64_arithmetic_serves, else the float32 kernels + two finishing steps): un-batched
     parameters are broadcast, a Q that is not SPD raises.  Returns the QPSolution; nothing is recorded for autograd.
     warm_start: a qpth_amd.WarmStart, as for QPFunction(warm_start=...) -- the loop starts at the holder's (lam, slacks) and
-    the holder takes this solve's."""
+    the holder takes this solve's.
+    rho: soft inequality rows, as the seventh input of QPFunction's callable: (nBatch, nineq), (nineq,), () or a
+    float, > 0, +inf = a hard row.  vjp_many(want=(..., "rho")) and jacobian(wrt=(..., "rho")) then differentiate in it.
+    float32 inputs need a size that runs in float64 arithmetic (f64_arithmetic_serves): the finishing steps of the other
+    sizes evaluate residuals of the hard QP."""
     with torch.no_grad():
         nBatch = extract_nBatch(Q, p, G, h, A, b)
         nineq, nz = G.size(-2), G.size(-1)
         neq = A.size(-2) if A.nelement() > 0 else 0
         assert(neq > 0 or nineq > 0)
         wide = Q.dtype == torch.float32 and f64_arithmetic_serves(nz, nineq, neq, _lib.backend_for(Q))
+        rho_dim = None
+        if rho is not None:
+            rho = as_rho(rho, Q, nineq, nBatch)
+            if Q.dtype == torch.float32 and not wide:
+                raise ValueError("qpth_amd: rho with float32 inputs at a size the float32 kernels serve with finishing steps on the "
+                                 "residuals of the hard QP; use float64 inputs, or QPFunction(refine=0)")
+            rho_dim = rho.dim()
+            rho = rho.detach().expand(nineq).unsqueeze(0) if rho_dim < 2 else rho.detach()
+            nBatch = max(nBatch, rho.size(0))
         params, shared = zip(*[expandParam(X.detach(), nBatch, nd) for X, nd in zip((Q, p, G, h, A, b), (3, 2, 3, 2, 3, 2))])
         Qe, pe, Ge, he, Ae, be = params
-        fac = KKTFactors.build(Qe, Ge, Ae, nBatch, wide=wide)
+        fac = KKTFactors.build(Qe, Ge, Ae, nBatch, wide=wide, w=None if rho is None else rho.reciprocal())
         warm = warm_start.pair(nBatch, nineq, Q.dtype, Q.device) if warm_start is not None else None
         res = fac.ipm(pe, he, be, eps, maxIter, notImprovedLim, want_trace=(verbose == 1), warm=warm,
                       warm_floor=warm_start.floor if warm is not None else 1e-2)
@@ -148,4 +172,4 @@ def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd
             _print_trace(res)
         if verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
             print(pdipm_b.INACC_ERR)
-        return QPSolution(fac, res, params, shared, refine)
+        return QPSolution(fac, res, params, shared, refine, rho, rho_dim)

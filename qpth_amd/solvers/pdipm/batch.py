@@ -60,9 +60,14 @@ class _Handle:
             self.role, self.fac.B, self.fac.n, self.fac.m, self.fac.q, self.fac.blob.dtype)
 
 
-def pre_factor_kkt(Q, G, A):
-    """Perform all one-time factorizations and cache relevant matrix products."""
-    fac = _dp.KKTFactors.build(Q, G, A)
+def pre_factor_kkt(Q, G, A, rho=None):
+    """Perform all one-time factorizations and cache relevant matrix products.
+    rho (nBatch, nineq), (nineq,), () or a number, > 0, +inf = a hard row: the factors of the QP with the penalty 1/2 sum rho_i t_i^2 on
+    the violation of G z <= h + t; every later call on the handles then serves that QP."""
+    if rho is not None:
+        rho = _dp.as_rho(rho, Q, G.size(-2), _dp._batch_of(Q, G, A))
+        rho = rho.expand(G.size(-2)) if rho.dim() == 0 else rho
+    fac = _dp.KKTFactors.build(Q, G, A, w=None if rho is None else rho.reciprocal())
     fac.raise_on_failure()
     return _Handle(fac, "Q_LU"), _Handle(fac, "S_LU"), _Handle(fac, "R")
 
