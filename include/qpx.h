@@ -17,6 +17,7 @@
  *   qpx_jvp ............... (no reference counterpart)            QPFunctionFn.jvp: forward mode, the adjoint of qpx_backward(_duals)
  *   qpx_ipm_warm .......... (no reference counterpart)            qpx_ipm entered at a previous solution's (lam, slacks)
  *   qpx_factor_solve_kkt_multi  (no reference counterpart)       factor_kkt once, solve_kkt for K right-hand sides per QP: Jacobians
+ *   qpx_backward2 ......... (no reference counterpart)            the second-order pass: the gradient of <W, qpx_backward's gradients>
  *   qpx_pre_factor_soft ... (no reference counterpart)            qpx_pre_factor with a quadratic penalty on the violation of chosen rows of G z <= h
  *
  * Conventions
@@ -291,6 +292,32 @@ int qpx_factor_solve_kkt_multi(int dtype, int B, int n, int m, int q, int K, voi
                                const void* d, const void* rx, const void* rs, const void* rz, const void* ry,
                                void* dx, void* ds, void* dz, void* dy,
                                int32_t* status, qpx_stream_t stream);
+
+/* Additive after v8 (QPX_ABI_VERSION stays 8): the SECOND-ORDER pass of the backward -- what torch.autograd.grad(...,
+ * create_graph=True) differentiates.  At the solution (zhat, lam, slack, nu), with (dx, dz, dy) the KKT solution a call of
+ * qpx_backward(_duals) returned for cotangents (dl_dz, dl_dlam, dl_dnu), and W_Q (B,n,n), W_p (B,n), W_G (B,m,n), W_h (B,m),
+ * W_A (B,q,n), W_b (B,q) cotangents on that call's six gradients (each with its batch stride in elements, 0 = shared; NULL = zero):
+ * the gradient of  psi = <W_Q, dQ> + <W_p, dp> + <W_G, dG> + <W_h, dh> + <W_A, dA> + <W_b, db>  per QP
+ *   - with respect to (dl_dz, dl_dlam, dl_dnu): zdot (B,n) (required), lamdot (B,m), nudot (B,q) (NULL = skip) -- qpx_jvp's
+ *     (dzhat, dlam, dnu) along W;
+ *   - with respect to the six parameters: HQ (B,n,n), Hp (B,n), HG (B,m,n), Hh (B,m), HA (B,q,n), Hb (B,q), each NULL = not
+ *     wanted: nothing is computed or written for it.
+ * One launch, one factorisation of T = R + diag(1/d) per QP, two solves, the second right-hand side formed from the first
+ * solution on the chip (DESIGN 4.9 has the closed form).  Second derivatives of a QP's solution exist only under strict
+ * complementarity (no row with lam_i = s_i = 0).  No refinement.  dtype QPX_F64 or QPX_F32_WIDE (W, inputs and outputs float32
+ * then), where qpx_backward2_supported returns 1 under the calling thread's knob: every form of the thread-grid / tile kernels
+ * (nz+neq+nineq <= 208) that the default dispatch picks; QPX_F32, the large-QP family and the two-wave tile forms of the A/B
+ * knob return QPX_ERR_UNSUPPORTED -- compose the pass from qpx_jvp and qpx_backward_duals there (qpth_amd/kkt.py:
+ * KKTFactors.backward2).  A breakdown of the factorisation ORs QPX_ST_KKT_BREAKDOWN into status, as the single solve does. */
+int qpx_backward2_supported(int dtype, int n, int m, int q);
+int qpx_backward2(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac,
+                  const void* zhat, const void* lam, const void* slack, const void* nu,
+                  const void* dx, const void* dz, const void* dy,
+                  const void* W_Q, int64_t sWQ, const void* W_p, int64_t sWp, const void* W_G, int64_t sWG,
+                  const void* W_h, int64_t sWh, const void* W_A, int64_t sWA, const void* W_b, int64_t sWb,
+                  void* zdot, void* lamdot, void* nudot,
+                  void* HQ, void* Hp, void* HG, void* Hh, void* HA, void* Hb,
+                  int32_t* status, qpx_stream_t stream);
 
 /* v6: the FINISHING STAGE as one kernel -- `steps` iterations of the reference's PDIPM loop in the original variables
  * (qpth/solvers/pdipm/batch.py:92-198: affine + centring-corrector Newton steps, step lengths batch.py:189-198) started

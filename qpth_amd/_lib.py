@@ -56,6 +56,10 @@ _SIGNATURES = {
                      _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "qpx_multi_supported": (_i, [_i, _i, _i, _i]),
     "qpx_factor_solve_kkt_multi": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qpx_backward2_supported": (_i, [_i, _i, _i, _i]),
+    "qpx_backward2": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qpx_polish_supported": (_i, [_i, _i, _i, _i]),
     "qpx_polish": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                         _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -231,6 +235,19 @@ class QpxLib:
             t[0].ptr, t[0].stride, t[1].ptr, t[1].stride, t[2].ptr, t[2].stride, t[3].ptr, t[3].stride,
             t[4].ptr, t[4].stride, t[5].ptr, t[5].stride, _ptr(dzhat), _ptr(dlam), _ptr(dnu), _ptr(dslack),
             int(refine), Qp.ptr, Qp.stride, Gp.ptr, Gp.stride, Ap.ptr, Ap.stride, _ptr(status), _stream(factors)))
+
+    # -- the second-order pass of the backward: one launch, one factorisation, two dependent solves
+    def backward2(self, B, n, m, q, factors, sfac, zhat, lam, slack, nu, dx, dz, dy, WQ, Wp, WG, Wh, WA, Wb,
+                  zdot, lamdot, nudot, HQ, Hp, HG, Hh, HA, Hb, status, wide=False):
+        """dx, dz, dy: the first backward's KKT solution, dense (B, .); WQ .. Wb: cotangents on its six gradients, any may be
+        None (zero), shared ones go in with batch stride 0 (Param); lamdot, nudot, HQ .. Hb: any may be None (not wanted)"""
+        t = [Param(WQ, 3), Param(Wp, 2), Param(WG, 3), Param(Wh, 2), Param(WA, 3), Param(Wb, 2)]
+        self.check(self.dll.qpx_backward2(
+            _code(factors, wide), B, n, m, q, _ptr(factors), int(sfac), _ptr(zhat), _ptr(lam), _ptr(slack), _ptr(nu),
+            _ptr(dx), _ptr(dz), _ptr(dy),
+            t[0].ptr, t[0].stride, t[1].ptr, t[1].stride, t[2].ptr, t[2].stride, t[3].ptr, t[3].stride,
+            t[4].ptr, t[4].stride, t[5].ptr, t[5].stride, _ptr(zdot), _ptr(lamdot), _ptr(nudot),
+            _ptr(HQ), _ptr(Hp), _ptr(HG), _ptr(Hh), _ptr(HA), _ptr(Hb), _ptr(status), _stream(factors)))
 
     # -- batch.py:92-198 in the original variables, as a finishing stage (KKTSolvers.IR_UNOPT, float32 refine=k)
     def polish(self, B, n, m, q, Q, p, G, h, A, b, factors, sfac, steps, refine, zhat, nu, lam, slack, best_resid, status):

@@ -369,6 +369,51 @@ int api_jvp(int io32, int B, int n, int m, int q, void* factors, int64_t sfac, c
     return api_kkt<T, 0>(a, stream);
 }
 
+// The second-order pass of the backward (qpx_backward2): the fourth role of the KKT forms (qpx_forms.h: kKktB2Role), in float64
+// arithmetic.  Which form serves a size follows api_kkt's rule; a form without the role -- the two-wave tile forms, reachable
+// through the A/B knob alone -- declines, it never falls through to a kernel that reads another image of the blob.
+inline bool b2_tile_form(int nbt, int nw, bool ch)
+{
+#define QPX_PICK(NBL, NW, CH) if (nbt == NBL && nw == NW && ch == CH) return true;
+    QPX_FORMS_KKT_B2_TILE(QPX_PICK)
+#undef QPX_PICK
+    return false;
+}
+// (B: the batch the tile forms' waves per QP depend on; every default choice has the role, so only the knob matters)
+inline bool b2_served(int dtype, int n, int m, int q, int B)
+{
+    if (dtype == QPX_F32 || !use_grid(n, m, q) || n > 4 * kWave) return false;
+    const int nbt = tile_nb(m);
+    if ((g_grid_size == 0 || g_grid_size == 1) && nbt > 0) {
+        const int nw = tile_waves(nbt, B);
+        return b2_tile_form(nbt, nw, tile_chain(nbt, nw));
+    }
+    return grid_nb(m) > 0;
+}
+inline int api_backward2(KktArgs<double>& a, void* stream)
+{
+    const int n = a.n, m = a.m, q = a.q;
+    a.images = blob_images<double>(n, m, q);
+    const int nbt = tile_nb(m);
+    if ((g_grid_size == 0 || g_grid_size == 1) && nbt > 0) {
+        const int nw = tile_waves(nbt, a.B);
+        const bool ch = tile_chain(nbt, nw);
+        const size_t tb = lds_elems_kkt_b2_tile(nbt, nw, n, q, ch) * sizeof(double);
+        if (tb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
+#define QPX_PICK(NBL, NW, CH) if (nbt == NBL && nw == NW && ch == CH) return launch_kkt_tile<kKktB2Role + NBL, NW, false, CH>(a, tb, stream);
+        QPX_FORMS_KKT_B2_TILE(QPX_PICK)
+#undef QPX_PICK
+        return QPX_ERR_UNSUPPORTED;
+    }
+    const int nbg = grid_nb(m);
+    const size_t gb = lds_elems_kkt_b2_grid(16, nbg, n, q) * sizeof(double);
+    if (gb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
+#define QPX_PICK(NBL) if (nbg == NBL) return launch_kkt_grid<double, kKktB2Role + NBL, false>(a, gb, stream);
+    QPX_FORMS_KKT_GRID(QPX_PICK)
+#undef QPX_PICK
+    return QPX_ERR_UNSUPPORTED;
+}
+
 // the finishing stage: every family has it (thread-grid / tile kernels: one kernel, the blob's register image of R decides the
 // form; large-QP family: qpx_big_polish.h)
 inline bool polish_served(int dtype, int n, int m, int q)
@@ -678,6 +723,41 @@ int qpx_jvp(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac, 
                                     th, sth, tA, stA, tb, stb, dzhat, dlam, dnu, dslack, refine, Q, sQ, G, sG, A, sA, status, stream);
     return qpx::api_jvp<float>(0, B, n, m, q, factors, sfac, zhat, lam, slack, nu, tQ, stQ, tp, stp, tG, stG, th, sth, tA, stA,
                                tb, stb, dzhat, dlam, dnu, dslack, refine, Q, sQ, G, sG, A, sA, status, stream);
+}
+
+int qpx_backward2_supported(int dtype, int n, int m, int q)
+{
+    if (qpx::check_dims(dtype, 1, n, m, q) != QPX_OK) return 0;
+    // (the forms the default dispatch picks have the role at every batch size: a small and a large batch cover both of its choices)
+    return qpx::b2_served(dtype, n, m, q, 1) && qpx::b2_served(dtype, n, m, q, 1 << 20) ? 1 : 0;
+}
+
+int qpx_backward2(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat, const void* lam,
+                  const void* slack, const void* nu, const void* dx, const void* dz, const void* dy,
+                  const void* W_Q, int64_t sWQ, const void* W_p, int64_t sWp, const void* W_G, int64_t sWG,
+                  const void* W_h, int64_t sWh, const void* W_A, int64_t sWA, const void* W_b, int64_t sWb,
+                  void* zdot, void* lamdot, void* nudot, void* HQ, void* Hp, void* HG, void* Hh, void* HA, void* Hb,
+                  int32_t* status, qpx_stream_t stream)
+{
+    const int e = qpx::check_dims(dtype, B, n, m, q);
+    if (e) return e;
+    if (!factors || !zhat || !lam || !slack || !dx || !dz || !zdot || (q > 0 && (!nu || !dy))) return QPX_ERR_ARG;
+    if (sWQ < 0 || sWp < 0 || sWG < 0 || sWh < 0 || sWA < 0 || sWb < 0) return QPX_ERR_ARG;
+    if (!qpx::b2_served(dtype, n, m, q, B)) return QPX_ERR_UNSUPPORTED;
+    qpx::KktArgs<double> a{};
+    a.io32 = dtype == QPX_F32_WIDE;
+    a.B = B; a.n = n; a.m = m; a.q = q; a.fac = (double*)factors; a.fac_stride = (size_t)sfac;
+    a.zhat = (const double*)zhat; a.lam = (const double*)lam; a.slack = (const double*)slack; a.nu = (const double*)nu;
+    a.rx = (const double*)dx; a.rz = (const double*)dz; a.ry = q > 0 ? (const double*)dy : nullptr;      // the first backward's KKT solution
+    a.jvp = 1;
+    a.tQ = (const double*)W_Q; a.tp = (const double*)W_p; a.tG = (const double*)W_G; a.th = (const double*)W_h;
+    a.tA = q > 0 ? (const double*)W_A : nullptr; a.tb = q > 0 ? (const double*)W_b : nullptr;
+    a.stQ = sWQ; a.stp = sWp; a.stG = sWG; a.sth = sWh; a.stA = sWA; a.stb = sWb;
+    a.dx = (double*)zdot; a.dz = (double*)lamdot; a.dy = q > 0 ? (double*)nudot : nullptr;
+    a.dQ = (double*)HQ; a.dp = (double*)Hp; a.dG = (double*)HG; a.dh = (double*)Hh;
+    a.dA = q > 0 ? (double*)HA : nullptr; a.db = q > 0 ? (double*)Hb : nullptr;
+    a.status = status;
+    return qpx::api_backward2(a, stream);
 }
 
 int qpx_polish_supported(int dtype, int n, int m, int q)

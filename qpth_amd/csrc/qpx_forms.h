@@ -30,6 +30,12 @@ constexpr int kKktMultiRole = 64;
 // workgroup of a CU.  qpth_amd/kkt.py: MULTI_RHS_BLOCK.
 constexpr int kKktMultiRB = 4;
 
+// A fourth role, float64 arithmetic only: the second-order pass of the backward (qpx_backward2; qpx_grid.h: kkt_b2_role) -- two
+// dependent solves behind one factorisation.  It travels like the third, block / tile rows + kKktB2Role, and exists for the
+// forms of QPX_FORMS_KKT_B2_TILE / every thread-grid form below (the tile forms the dispatcher picks by default: the two-wave
+// forms, reachable through the A/B knob alone, decline -- qpx_backward2_supported).
+constexpr int kKktB2Role = 128;
+
 // Every pre-factorisation form exists a second time for soft rows (qpx_pre_factor_soft): blocks / tile rows + kPrefacSoft in
 // the form's FIRST parameter, as above (sweep_body / prefac_tile_body decode it).  The hard forms hold none of the soft
 // rows' code: their registers are the ones they had without it.
@@ -52,5 +58,6 @@ constexpr int kPrefacSoft = 64;
     X(7, 4, 2, true) X(7, 4, 4, true) X(4, 4, 1, true) X(4, 4, 2, true) X(4, 4, 4, true)
 #define QPX_FORMS_KKT_TILE(X) \
     X(1, 1, false) X(2, 1, false) X(4, 1, false) X(4, 2, false) X(7, 2, false) X(7, 4, true) X(4, 4, true)   // each in the three roles, as above
+#define QPX_FORMS_KKT_B2_TILE(X) X(1, 1, false) X(2, 1, false) X(4, 1, false) X(7, 4, true) X(4, 4, true)            // the second-order role (kKktB2Role)
 #define QPX_FORMS_POLISH_TILE(X) X(1, 1, false) X(2, 1, false) X(4, 1, false) X(4, 4, true) X(7, 4, true)
 #define QPX_FORMS_PREFAC_TILE(X) X(4, false) X(7, false) X(4, true) X(7, true)    // (tile rows of nz + neq, with equalities)

@@ -1962,11 +1962,164 @@ QPX_DEV void kkt_multi_body(const Block& b, const KktArgs<T>& a, int qp, T* lds)
     Mat::with_role(g, [&](const auto& gp) { kkt_multi_role<T, Mat, RB>(b, a, qp, lds, gp); });
 }
 
-// (NBL >= kKktMultiRole: the multi-right-hand-side role of the form with NBL - kKktMultiRole blocks, qpx_forms.h)
+// ------------------------------------------------------------------------------------------
+// The SECOND-ORDER pass of the backward in one launch (qpx_backward2): the gradient of
+//   psi = <W_Q, dQ> + <W_p, dp> + <W_G, dG> + <W_h, dh> + <W_A, dA> + <W_b, db>
+// -- dQ .. db the six gradients of the first backward, whose KKT solution (bx, bz, by) the caller passes in (KktArgs::rx, rz,
+// ry) -- with respect to the first backward's cotangents, (zdot, lamdot, nudot) -> KktArgs::dx, dz, dy, and to the six
+// parameters, HQ .. Hb -> KktArgs::dQ .. db.  W = KktArgs::tQ .. tb with their strides.  Two solves with the backward's matrix
+// behind ONE factorisation of T = R + diag(1/d), the second right-hand side depending on the first solution:
+//   1. (zdot, lamdot, nudot) = the tangent solve of forward mode along W: kkt_jvp_rhs as it stands;
+//   2. (ex, ez', ey) for the right-hand side (g_z', g_lam + u/d, g_nu), u = a lamdot, a = bz / clamp(lam):
+//        g_z' = S bx + W_G^T bz + W_A^T by,  g_lam = W_G bx + u/d,  g_nu = W_A bx
+//      -- kkt_jvp_rhs once more, at (bx, bz, by) in the places of (zhat, lam, nu) and without the vector cotangents, plus
+//      2 u/d on the inequality rows.  The closed form's g_z has G^T u as well, and the blob holds no G: by
+//      M (0, u, 0) = (G^T u, -u/d, 0) that term is the shift ez = ez' - u of the solution with u/d added to g_lam, and every
+//      output needs ez + u = ez' only.
+// Both right-hand sides and the factor-free halves of both applications of the condensed inverse (kkt_mat_role: products) are
+// formed BEFORE R's image is loaded, while the tile registers are free; behind the factorisation run the two solves.  Then
+//   HQ = 1/2 (bx zdot' + zdot bx' + ex zhat' + zhat ex'),  Hp = ex,  HG = lamdot bx' + bz zdot' + ez' zhat' + lam ex',  Hh = -ez',
+//   HA = nudot bx' + by zdot' + ey zhat' + nu ex',  Hb = -ey.
+// No refinement.  A breakdown of the factorisation sets the status bit and returns zeros for lamdot, ez', as the single solve.
+template <class T, class Mat, class P>
+QPX_DEV void kkt_b2_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, const P& g)
+{
+    constexpr int M8 = Mat::MP, NT = Mat::NT;
+    const int n = a.n, m = a.m, q = a.q, io32 = a.io32;
+    const FacLayout lay = fac_layout(n, m, q, a.images);
+    const T* F = a.fac + (size_t)qp * a.fac_stride;
+    const size_t v = align4(max2(max2((size_t)n, (size_t)M8), (size_t)q));      // lds_elems_kkt_b2
+    T* rd = lds;
+    T* vD = rd + v;       // 1/d, 1 on the pad
+    T* vTm = vD + v;
+    T* vRX = vTm + v;     // first solve: right-hand side (n, q, M8) ...
+    T* vRY = vRX + v;
+    T* vRH = vRY + v;
+    T* vDX = vRH + v;     // ... and solution zdot (n), lamdot (M8), nudot (q)
+    T* vDZ = vDX + v;
+    T* vDY = vDZ + v;
+    T* vGX = vDY + v;     // second solve: right-hand side ...
+    T* vGY = vGX + v;
+    T* vGH = vGY + v;
+    T* vEX = vGH + v;     // ... and solution ex (n), ez' (M8), ey (q)
+    T* vEZ = vEX + v;
+    T* vEY = vEZ + v;
+    T* vZH = vEY + v;     // zhat (n), lam (M8, 0 on the pad), nu (q)
+    T* vLM = vZH + v;
+    T* vNU = vLM + v;
+    T* vBX = vNU + v;     // the first backward's bx (n), bz (M8, 0 on the pad), by (q)
+    T* vBZ = vBX + v;
+    T* vBY = vBZ + v;
+    T* scr = vBY + v;     // Mat::scratch_elems()
+
+    kkt_jvp_rhs<T, Mat>(b, a, qp, vD, vRX, vRY, vRH, vZH, vLM, vNU);
+    {
+        // the products with W_Q, W_G, W_A once more, at the first backward's solution (the 1/d this pass forms from its
+        // "lam" is not one: into the temporary of the solves)
+        KktArgs<T> a2 = a;
+        a2.zhat = a.rx; a2.lam = a.rz; a2.nu = a.ry;
+        a2.tp = nullptr; a2.th = nullptr; a2.tb = nullptr;
+        kkt_jvp_rhs<T, Mat>(b, a2, qp, vTm, vGX, vGY, vGH, vBX, vBZ, vBY);
+    }
+    // the halves of the condensed inverse that need no factor (kkt_mat_role): rH += M rX + W rY, oX = -K rX
+    auto products = [&](const T* rX, const T* rY, T* rH, T* oX) {
+        block_matTvec2<T, 1, 0, T, (M8 > 64 ? 16 : 8)>(b, rH, F + lay.MT, m, oX, F + lay.Kneg, n, rX, n);
+        if (q > 0) {
+            Mat::sync(b);
+            for (int j = b.tid; j < m; j += NT) {
+                T acc = rH[j];
+                for (int r = 0; r < q; ++r) acc = fma_(F[lay.W + (size_t)j * q + r], rY[r], acc);
+                rH[j] = acc;
+            }
+        }
+        Mat::sync(b);
+    };
+    products(vRX, vRY, vRH, vDX);
+    products(vGX, vGY, vGH, vEX);
+    typename Mat::Regs E;
+    const bool ok = kkt_factor<T, Mat>(b, g, E, Mat::image(F, lay), vD, scr, rd, m, [] {});
+    if (!ok && b.tid == 0 && a.status) a.status[qp] |= QPX_ST_KKT_BREAKDOWN;
+    // oZ = -T^-1 rH,  oX += -M^T oZ - N rY,  oY = S11^-1 rY - N^T rX - W^T oZ      (kkt_mat_role: finish)
+    auto finish = [&](const T* rX, const T* rY, T* rH, T* oZ, T* oX, T* oY) {
+        if (ok) Mat::solve_neg(b, g, E, rd, m, rH, oZ, vTm, scr);
+        else {
+            for (int i = b.tid; i < M8; i += NT) oZ[i] = T(0);
+            Mat::sync(b);
+        }
+        block_matvec16<T, 2>(b, oX, F + lay.MT, oZ, n, m);
+        if (q > 0) {
+            Mat::sync(b);
+            block_matTvec<T, 1>(b, oX, F + lay.NTn, rY, q, n);
+            for (int r = b.tid; r < q; r += NT) {
+                T acc = 0;
+                for (int c2 = 0; c2 < q; ++c2) acc = fma_(F[lay.S11i + (size_t)r * q + c2], rY[c2], acc);
+                for (int k = 0; k < n; ++k) acc = fma_(F[lay.NTn + (size_t)r * n + k], rX[k], acc);
+                for (int j = 0; j < m; ++j) acc = fma_(-F[lay.W + (size_t)j * q + r], oZ[j], acc);
+                oY[r] = acc;
+            }
+        }
+        Mat::sync(b);
+    };
+    finish(vRX, vRY, vRH, vDZ, vDX, vDY);
+    // rH of the second solve is rs/d - rz = -(g_lam + u/d): -W_G bx (from above, with M g_z' + W g_nu added) - 2 u/d
+    for (int i = b.tid; i < m; i += NT) {
+        const T l = vLM[i];
+        const T u = vBZ[i] / ((l < T(1e-8)) ? T(1e-8) : l) * vDZ[i];
+        vGH[i] -= T(2) * u * vD[i];
+    }
+    Mat::sync(b);
+    finish(vGX, vGY, vGH, vEZ, vEX, vEY);
+
+    for (int i = b.tid; i < n; i += NT) {
+        put_(a.dx, io32, (size_t)qp * n + i, vDX[i]);
+        if (a.dp) put_(a.dp, io32, (size_t)qp * n + i, vEX[i]);
+    }
+    for (int i = b.tid; i < m; i += NT) {
+        if (a.dz) put_(a.dz, io32, (size_t)qp * m + i, vDZ[i]);
+        if (a.dh) put_(a.dh, io32, (size_t)qp * m + i, -vEZ[i]);
+    }
+    for (int i = b.tid; i < q; i += NT) {
+        if (a.dy) put_(a.dy, io32, (size_t)qp * q + i, vDY[i]);
+        if (a.db) put_(a.db, io32, (size_t)qp * q + i, -vEY[i]);
+    }
+    if (a.dQ) {
+        const size_t o = (size_t)qp * n * n;
+        for (int idx = b.tid; idx < n * n; idx += NT) {
+            const int r = idx / n, c = idx - r * n;
+            put_(a.dQ, io32, o + idx, T(0.5) * (vBX[r] * vDX[c] + vDX[r] * vBX[c] + vEX[r] * vZH[c] + vZH[r] * vEX[c]));
+        }
+    }
+    if (a.dG) {
+        const size_t o = (size_t)qp * m * n;
+        for (int idx = b.tid; idx < m * n; idx += NT) {
+            const int r = idx / n, c = idx - r * n;
+            put_(a.dG, io32, o + idx, vDZ[r] * vBX[c] + vBZ[r] * vDX[c] + vEZ[r] * vZH[c] + vLM[r] * vEX[c]);
+        }
+    }
+    if (q > 0 && a.dA) {
+        const size_t o = (size_t)qp * q * n;
+        for (int idx = b.tid; idx < q * n; idx += NT) {
+            const int r = idx / n, c = idx - r * n;
+            put_(a.dA, io32, o + idx, vDY[r] * vBX[c] + vBY[r] * vDX[c] + vEY[r] * vZH[c] + vNU[r] * vEX[c]);
+        }
+    }
+}
+
+template <class T, class Mat>
+QPX_DEV void kkt_b2_body(const Block& b, const KktArgs<T>& a, int qp, T* lds)
+{
+    typename Mat::Pos g(b);
+    g.assign(b, reinterpret_cast<int*>(lds));
+    Mat::with_role(g, [&](const auto& gp) { kkt_b2_role<T, Mat>(b, a, qp, lds, gp); });
+}
+
+// (NBL >= kKktMultiRole: the multi-right-hand-side role of the form with NBL - kKktMultiRole blocks, >= kKktB2Role: its
+// second-order role, qpx_forms.h)
 template <class T, int GS, int NBL, bool kBackward>
 QPX_DEV void kkt_grid_body(const Block& b, const KktArgs<T>& a, int qp, T* lds)
 {
-    if constexpr (NBL >= kKktMultiRole) kkt_multi_body<T, GridMat<T, GS, NBL - kKktMultiRole>, kKktMultiRB>(b, a, qp, lds);
+    if constexpr (NBL >= kKktB2Role) kkt_b2_body<T, GridMat<T, GS, NBL - kKktB2Role>>(b, a, qp, lds);
+    else if constexpr (NBL >= kKktMultiRole) kkt_multi_body<T, GridMat<T, GS, NBL - kKktMultiRole>, kKktMultiRB>(b, a, qp, lds);
     else kkt_mat_body<T, GridMat<T, GS, NBL>, kBackward>(b, a, qp, lds);
 }
 
@@ -2352,6 +2505,17 @@ QPX_LAYOUT_HD size_t lds_elems_kkt_grid(int gs, int nbl, int n, int q)
 {
     const size_t mg = (size_t)gs * nbl;
     return lds_elems_kkt_mat(mg, 2 * mg + 4 + (size_t)nbl * gs * gs, n, q);
+}
+// ... of its second-order role (kkt_b2_role): 21 vectors + the scratch
+QPX_LAYOUT_HD size_t lds_elems_kkt_b2(size_t mp, size_t scratch, int n, int q)
+{
+    const size_t v = align4(max2(max2((size_t)n, mp), (size_t)q));
+    return 21 * v + scratch;
+}
+QPX_LAYOUT_HD size_t lds_elems_kkt_b2_grid(int gs, int nbl, int n, int q)
+{
+    const size_t mg = (size_t)gs * nbl;
+    return lds_elems_kkt_b2(mg, 2 * mg + 4 + (size_t)nbl * gs * gs, n, q);
 }
 // ... of its multi-right-hand-side role (kkt_multi_role): rd, 1/d, a temporary; per right-hand side of a block rx, dx (n),
 // ry, dy (q), the solve's right-hand side and dz (mp); the scratch

@@ -49,6 +49,13 @@ template <auto K, class... Args> static int launch_kernel(dim3 grid, int threads
     return hipGetLastError() == hipSuccess ? QPX_OK : QPX_ERR_LAUNCH;
 }
 
+// (is QPX_TU_REAL double?  The second-order role of the KKT forms, kKktB2Role, is built in float64 arithmetic only)
+#define QPX_REAL_IS_float 0
+#define QPX_REAL_IS_double 1
+#define QPX_CAT2(a, b) a##b
+#define QPX_CAT(a, b) QPX_CAT2(a, b)
+#define QPX_REAL_IS_DOUBLE QPX_CAT(QPX_REAL_IS_, QPX_TU_REAL)
+
 #if QPX_TU_KERNEL == 5
 // (at least two workgroups per CU -- <= 256 registers -- at every size: the largest instantiation holds 91 matrix entries per thread)
 template <class T, int NBL> __global__ __launch_bounds__(256, 2) void k_sweep(PrefactorArgs<T> a)
@@ -80,7 +87,7 @@ template <class T, int NBL, int NS> int launch_ipm_grid(const IpmArgs<T>& a, siz
 #define QPX_INST(NBL, NS) template int launch_ipm_grid<QPX_TU_REAL, NBL, NS>(const IpmArgs<QPX_TU_REAL>&, size_t, void*);
 QPX_FORMS_IPM_GRID(QPX_INST)
 #elif QPX_TU_KERNEL == 7
-// (NBL >= kKktMultiRole: the form's multi-right-hand-side role, qpx_forms.h)
+// (NBL >= kKktMultiRole: the form's multi-right-hand-side role, >= kKktB2Role: its second-order role, qpx_forms.h)
 template <class T, int NBL, bool kBw> __global__ __launch_bounds__(256, (NBL % kKktMultiRole <= 7 ? 2 : 1)) void k_kkt_grid(KktArgs<T> a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char qpx_smem[];
@@ -96,6 +103,10 @@ template <class T, int NBL, bool kBw> int launch_kkt_grid(const KktArgs<T>& a, s
     template int launch_kkt_grid<QPX_TU_REAL, NBL, true>(const KktArgs<QPX_TU_REAL>&, size_t, void*);     \
     template int launch_kkt_grid<QPX_TU_REAL, kKktMultiRole + NBL, false>(const KktArgs<QPX_TU_REAL>&, size_t, void*);
 QPX_FORMS_KKT_GRID(QPX_INST)
+#if QPX_REAL_IS_DOUBLE
+#define QPX_INSTB2(NBL) template int launch_kkt_grid<double, kKktB2Role + NBL, false>(const KktArgs<double>&, size_t, void*);
+QPX_FORMS_KKT_GRID(QPX_INSTB2)
+#endif
 // the finishing stage (qpx_polish) on the thread grid
 template <class T, int NBL> __global__ __launch_bounds__(256) void k_polish_grid(PolishArgs<T> a)
 {
@@ -202,8 +213,10 @@ template <int NBL, int NW, bool kBw, bool CH> int launch_kkt_tile(const KktArgs<
     template int launch_kkt_tile<NBL, NW, false, CH>(const KktArgs<double>&, size_t, void*);       \
     template int launch_kkt_tile<NBL, NW, true, CH>(const KktArgs<double>&, size_t, void*);        \
     template int launch_kkt_tile<kKktMultiRole + NBL, NW, false, CH>(const KktArgs<double>&, size_t, void*);
+#define QPX_INSTKB2(NBL, NW, CH) template int launch_kkt_tile<kKktB2Role + NBL, NW, false, CH>(const KktArgs<double>&, size_t, void*);
 #if !defined(QPX_TILE_ONLY)
 QPX_FORMS_KKT_TILE(QPX_INSTK)
+QPX_FORMS_KKT_B2_TILE(QPX_INSTKB2)
 #endif
 #define QPX_INSTT(NBL, NW, NS, CH) template int launch_ipm_tile<NBL, NW, NS, CH>(const IpmArgs<double>&, size_t, void*);
 #if defined(QPX_TILE_ONLY)

@@ -1325,11 +1325,18 @@ QPX_LAYOUT_HD size_t lds_elems_kkt_multi_tile(int nbl, int nw, int n, int q, boo
     return lds_elems_kkt_multi(16 * (size_t)nbl, tile_scratch_elems(nbl, chain ? nw - 1 : nw, chain), n, q, kKktMultiRB);
 }
 
-// (NBL >= kKktMultiRole: the multi-right-hand-side role of the form with NBL - kKktMultiRole tile rows, qpx_forms.h)
+QPX_LAYOUT_HD size_t lds_elems_kkt_b2_tile(int nbl, int nw, int n, int q, bool chain = false)
+{
+    return lds_elems_kkt_b2(16 * (size_t)nbl, tile_scratch_elems(nbl, chain ? nw - 1 : nw, chain), n, q);
+}
+
+// (NBL >= kKktMultiRole: the multi-right-hand-side role of the form with NBL - kKktMultiRole tile rows, >= kKktB2Role: its
+// second-order role, qpx_forms.h)
 template <int NBL, int NW, bool kBackward, bool CH = false>
 QPX_DEV void kkt_tile_body(const Block& b, const KktArgs<double>& a, int qp, double* lds)
 {
-    if constexpr (NBL >= kKktMultiRole) kkt_multi_body<double, TileMat<NBL - kKktMultiRole, NW, CH>, kKktMultiRB>(b, a, qp, lds);
+    if constexpr (NBL >= kKktB2Role) kkt_b2_body<double, TileMat<NBL - kKktB2Role, NW, CH>>(b, a, qp, lds);
+    else if constexpr (NBL >= kKktMultiRole) kkt_multi_body<double, TileMat<NBL - kKktMultiRole, NW, CH>, kKktMultiRB>(b, a, qp, lds);
     else kkt_mat_body<double, TileMat<NBL, NW, CH>, kBackward>(b, a, qp, lds);
 }
 

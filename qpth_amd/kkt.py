@@ -524,7 +524,7 @@ a non-zero diagonal.
 
     # -- QPFunctionFn.backward (qp.py:127-182) ------------------------------------------------
     def backward(self, zhat, lam, slacks, nu, dl_dz, want=(True,) * 6, shared=(False,) * 6, refine=0,
-                 dl_dlam=None, dl_dnu=None, want_dz=False):
+                 dl_dlam=None, dl_dnu=None, want_dz=False, want_sol=False):
         """Gradients (dQ, dp, dG, dh, dA, db) for the parameters `want` asks for (ctx.needs_input_grad;
         the others come back as None and cost nothing).  A parameter flagged in `shared` is one the whole
         batch shares: its gradient is returned already reduced to the reference's `.mean(0)` (qp.py:159-177)
@@ -533,7 +533,9 @@ a non-zero diagonal.
         but not all three): the same launch with the right-hand side (dl_dz, 0, dl_dlam, dl_dnu) -- qpx_backward_duals,
         the exact adjoint of jvp(..., want_duals=True).
         want_dz: a seventh value behind the six, dz (B, m) of the KKT solution as the launch wrote it -- the gradient with
-        respect to the w of soft factors is -dz lam."""
+        respect to the w of soft factors is -dz lam.
+        want_sol: a last value behind those, (dx, dz, dy) -- the solution of the backward KKT system as the launch wrote it (dy
+        None without equality constraints): what backward2 differentiates through."""
         self._no_refine_on_soft(refine, "backward")
         B, n, m, q = self.B, self.n, self.m, self.q
         dt, dev = self.dtype, self.device
@@ -554,9 +556,9 @@ a non-zero diagonal.
         dp = buf(wp and not sp, B, n)
         dh = buf(wh and not sh, B, m)
         db = buf(wb and not sb, B, q)
-        dx = buf((wp and sp) or (wQ and sQ) or (wG and sG) or (wA and sA), B, n)
-        dz = buf((wh and sh) or (wG and sG) or want_dz, B, m)
-        dy = buf(q > 0 and ((wb and sb) or (wA and sA)), B, q)
+        dx = buf((wp and sp) or (wQ and sQ) or (wG and sG) or (wA and sA) or want_sol, B, n)
+        dz = buf((wh and sh) or (wG and sG) or want_dz or want_sol, B, m)
+        dy = buf(q > 0 and ((wb and sb) or (wA and sA) or want_sol), B, q)
         zh, lm, nv = self._vec(zhat, n, "zhat"), self._vec(lam, m, "lam"), self._vec(nu, q, "nu")
         gz, gl, gn = self._vec(dl_dz, n, "dl_dz"), self._vec(dl_dlam, m, "dl_dlam"), self._vec(dl_dnu, q, "dl_dnu")
         if gz is None and gl is None and gn is None:
@@ -587,6 +589,95 @@ a non-zero diagonal.
             if wb and sb:
                 db = torch.empty(q, dtype=dt, device=dev)
                 self.lib.batch_outer(dy, None, None, None, -1.0, db)
-        if want_dz:
-            return dQ, dp, dG, dh, dA, db, dz
-        return dQ, dp, dG, dh, dA, db
+        out = (dQ, dp, dG, dh, dA, db) + ((dz,) if want_dz else ())
+        return out + ((dx, dz, dy),) if want_sol else out
+
+    # -- the backward of the backward ------------------------------------------------
+    def backward2_fused(self):
+        """does qpx_backward2 serve these factors (under the knob they were built with)?"""
+        if self.soft or not hasattr(self.lib.dll, "qpx_backward2_supported"):
+            return False
+        code = _lib.QPX_F32_WIDE if self.wide else (_lib.QPX_F64 if self.dtype == torch.float64 else _lib.QPX_F32)
+        with self._knob():
+            return bool(self.lib.dll.qpx_backward2_supported(code, self.n, self.m, self.q))
+
+    def backward2(self, zhat, lam, slacks, nu, sol, W, want=(True,) * 6, fused=None):
+        """The second-order pass: for cotangents W = (W_Q, W_p, W_G, W_h, W_A, W_b) on the six PER-QP gradients a call of
+        backward() returned -- each None (zero) or of its gradient's shape, batched (B, ...) or one for the whole batch -- and
+        that call's KKT solution sol = (dx, dz, dy) (backward(want_sol=True)), the gradient of psi = sum_i <W_i, grad_i>
+          - with respect to that call's cotangents (dl_dz, dl_dlam, dl_dnu): (zdot, lamdot, nudot), nudot None without
+            equality constraints;
+          - with respect to the six parameters, per QP: (HQ, Hp, HG, Hh, HA, Hb), None where `want` does not ask.
+        Returns ((zdot, lamdot, nudot), (HQ, .., Hb)).  Two more solves with the matrix the backward factors (DESIGN 4.9 has
+        the closed form).  fused=None: one launch with one factorisation (qpx_backward2) where the library serves these
+        factors, else the COMPOSED path -- jvp(want_duals=True), elementwise and outer products in torch, backward(dl_dlam=,
+        dl_dnu=): the large-QP family (nz+neq+nineq > 208), float32 kernels, forms the fused entry declines.  True / False
+        force one or the other (True raises where the library declines).  Second derivatives of a QP's solution exist only
+        under strict complementarity; soft factors and refinement are not served.  No host sync."""
+        if self.soft:
+            raise RuntimeError("qpth_amd: second derivatives are not served on factors with soft rows (w / rho)")
+        B, n, m, q = self.B, self.n, self.m, self.q
+        dt, dev = self.dtype, self.device
+        dx, dz, dy = sol
+        shapes = ((n, n), (n,), (m, n), (m,), (q, n), (q,))
+        Ws = []
+        for X, shape, what in zip(W, shapes, ("Q", "p", "G", "h", "A", "b")):
+            if X is None or X.nelement() == 0 or (q == 0 and what in ("A", "b")):
+                Ws.append(None)
+                continue
+            if X.dtype != dt or X.device != dev:
+                raise RuntimeError("qpth_amd: the cotangent on the gradient of %s is %s on %s, the factors were built for %s on %s"
+                                   % (what, X.dtype, X.device, dt, dev))
+            if tuple(X.shape) not in (shape, (1,) + shape, (B,) + shape):
+                raise RuntimeError("qpth_amd: the cotangent on the gradient of %s has shape %s, expected %s, %s or %s"
+                                   % (what, tuple(X.shape), shape, (1,) + shape, (B,) + shape))
+            Ws.append(X)
+        want = [bool(w) for w in want]
+        if q == 0:
+            want[4] = want[5] = False
+        zh, lm, sl, nv = self._vec(zhat, n, "zhat"), self._vec(lam, m, "lam"), self._vec(slacks, m, "slacks"), self._vec(nu, q, "nu")
+        dx, dz, dy = self._vec(dx, n, "dx"), self._vec(dz, m, "dz"), self._vec(dy, q, "dy")
+        if fused is None:
+            fused = self.backward2_fused()
+        elif fused and not self.backward2_fused():
+            raise RuntimeError("qpth_amd: qpx_backward2 does not serve nz = %d, nineq = %d, neq = %d in this dtype under the "
+                               "current knob (qpx_backward2_supported)" % (n, m, q))
+        if fused:
+            def buf(flag, *shape):
+                return torch.empty(*shape, dtype=dt, device=dev) if flag else None
+            zd, ld, nd = buf(True, B, n), buf(True, B, m), buf(q > 0, B, q)
+            H = [buf(w, B, *shape) for w, shape in zip(want, shapes)]
+            with self._knob():
+                self.lib.backward2(B, n, m, q, self.blob, self.sfac, zh, lm, sl, nv, dx, dz, dy, *Ws, zd, ld, nd, *H,
+                                   self.status, wide=self.wide)
+            return (zd, ld, nd), tuple(H)
+        # composed: step 1, forward mode along W
+        zd, ld, nd = self.jvp(zh, lm, sl, nv, Ws, want_duals=True)
+        # step 2, the cotangents on the solution (a None W is zero)
+        WQ, Wp, WG, Wh, WA, Wb = [X if (X is None or X.dim() == len(sh) + 1) else X.unsqueeze(0) for X, sh in zip(Ws, shapes)]
+        # (the closed form's g_z has G^T u, u = a lamdot, as well: by M (0, u, 0) = (G^T u, -u/d, 0) that term is the shift
+        # ez = ez' - u of the solution for u/d added to g_lam, and HG, Hh need ez + u = ez' only -- as the kernel, no product with G)
+        lc = lm.clamp(min=1e-8)
+        u = dz / lc * ld
+        gz = torch.zeros(B, n, dtype=dt, device=dev)
+        gl = 2.0 * u * sl.clamp(min=1e-8) / lc               # a (G zdot + t_z) = u / d by row 2 of step 1, and u / d once more
+        gn = torch.zeros(B, q, dtype=dt, device=dev) if q else None
+        mv = lambda M_, x: torch.matmul(M_, x.unsqueeze(2)).squeeze(2)      # noqa: E731
+        if WQ is not None:
+            gz = gz + 0.5 * mv(WQ + WQ.transpose(1, 2), dx)
+        if WG is not None:
+            gz = gz + mv(WG.transpose(1, 2), dz)
+            gl = gl + mv(WG, dx)
+        if WA is not None:
+            gz = gz + mv(WA.transpose(1, 2), dy)
+            gn = gn + mv(WA, dx)
+        # step 3, one more backward with cotangents on the multipliers, plus the direct terms
+        H = list(self.backward(zh, lm, sl, nv, gz, want=want, dl_dlam=gl, dl_dnu=gn))
+        o = lambda x, y: x.unsqueeze(2) * y.unsqueeze(1)                  # noqa: E731
+        if want[0]:
+            H[0] = H[0] + 0.5 * (o(dx, zd) + o(zd, dx))
+        if want[2]:
+            H[2] = H[2] + o(ld, dx) + o(dz, zd)
+        if want[4]:
+            H[4] = H[4] + o(nd, dx) + o(dy, zd)
+        return (zd, ld, nd), tuple(H)

@@ -13,11 +13,14 @@ the backward's KKT system with the right-hand side formed from the input tangent
 QPFunction(duals=True) also returns the multipliers, differentiable in both modes: (zhat, nu, lam, slacks).
 QPFunction(warm_start=ws) starts the loop at the previous call's (lam, slacks) kept in a qpth_amd.WarmStart.
 QPFunction(...)(Q, p, G, h, A, b, rho) softens rows of G z <= h by a quadratic penalty, differentiable in rho too.
+The backward is itself differentiable once: torch.autograd.grad(..., create_graph=True) and a second grad give Hessian-vector
+products through the layer, one more launch with one factorisation and two solves (qpx_backward2).
 """
 from enum import Enum
 
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .kkt import KKTFactors, as_rho
@@ -56,6 +59,15 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                check_Q_spd=True, refine=None, duals=False, warm_start=None):
     """Returns f(Q, p, G, h, A, b, rho=None).  `refine`, `duals`, `warm_start` and the seventh input `rho` are what the reference
     does not have.
+    Second derivatives: under torch.autograd.grad(..., create_graph=True) the gradients carry a graph, and a second
+      grad -- Hessian-vector products, gradient penalties, losses on -dE/dx, MAML-style outer loops -- runs the second-order
+      pass: gradients flow to the first backward's cotangents (dl/dzhat, and dl/dlam, dl/dnu under duals=True) and to Q, p,
+      G, h, A, b, un-batched parameters included.  They exist only under STRICT COMPLEMENTARITY: at a solution with a row
+      where lam_i = s_i = 0 the solution map has a kink and the value returned is a one-sided one; rows with max(lam_i, s_i)
+      below ~1e-3 already make it ill-conditioned.  Not served, each a RuntimeError from the second grad: soft rows (rho),
+      refine > 0 (float32 inputs at sizes the float64 kernels do not serve run with refine=2 by default: pass refine=0), the
+      external-solver path; and third derivatives (the second-order pass is once differentiable).  Without create_graph
+      nothing changes: the same launches in the same order.
     rho: soft inequality rows,
           min 1/2 z'Qz + p'z + 1/2 sum_i rho_i t_i^2   s.t.  Gz <= h + t,  Az = b,
       solved in the kernels of the hard QP of the same (nz, nineq, neq) -- no augmented variables.  A tensor of the other
@@ -197,8 +209,41 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         zt, lt, nt = fac.jvp(ctx.zhat, ctx.lams, ctx.slacks, ctx.nus, (dQ, dp, dG, dh, dA, db), refine=rf, want_duals=True)
         return zt, nt, lt, None
 
+    class QPBackwardFn(Function):
+        """The first backward as a node of its own: _backward goes through it when it runs with grad mode on, i.e. under
+        torch.autograd.grad(..., create_graph=True), so that its gradients carry a graph.  forward is the launch _backward
+        makes otherwise and also keeps the solution (dx, dz, dy) of the backward KKT system; backward is the second-order
+        pass (KKTFactors.backward2): gradients flow to the incoming cotangents and to the six parameters.  It is
+        once differentiable: third derivatives are not offered."""
+        @staticmethod
+        def forward(c, st, dl_dzhat, dl_dlam, dl_dnu, Q_, p_, G_, h_, A_, b_):
+            out = st["fac"].backward(st["zhat"], st["lams"], st["slacks"], st["nus"], dl_dzhat, want=st["want"],
+                                     shared=st["shared"], refine=st["refine"], dl_dlam=dl_dlam, dl_dnu=dl_dnu,
+                                     want_dz=st["want_rho"], want_sol=True)
+            c.st, c.sol = st, out[-1]
+            c.set_materialize_grads(False)
+            return out[:-1]
+
+        @staticmethod
+        @once_differentiable
+        def backward(c, *W):
+            st = c.st
+            if st["unserved"]:
+                raise RuntimeError("qpth_amd: second derivatives (create_graph=True) are not served %s" % st["unserved"])
+            W, shared, nB = W[:6], st["shared"], st["nBatch"]
+            if all(w is None for w in W):
+                return (None,) * 10
+            # a parameter the batch shares got the batch MEAN of its per-QP gradients: the per-QP cotangent is W / nBatch, and
+            # its second-order gradient the SUM over the batch of the per-QP results
+            Wq = [None if w is None else (w / nB if sh else w) for w, sh in zip(W, shared)]
+            need = c.needs_input_grad
+            (zd, ld, nd), H = st["fac"].backward2(st["zhat"], st["lams"], st["slacks"], st["nus"], c.sol, Wq, want=need[4:10])
+            H = [None if x is None else (x.sum(0) if sh else x) for x, sh in zip(H, shared)]
+            return (None, zd if need[1] else None, ld if need[2] else None, nd if need[3] else None) + tuple(H)
+
     def _backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
         zhats, Q, p, G, h, A, b = ctx.saved_tensors[:7]
+        leaves = (Q, p, G, h, A, b)
         nBatch = extract_nBatch(Q, p, G, h, A, b)
         Q, Q_e = expandParam(Q, nBatch, 3)
         p, p_e = expandParam(p, nBatch, 2)
@@ -224,10 +269,19 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         # the batch instead of nBatch outer products.
         want = tuple(ctx.needs_input_grad[:6])
         want_rho = soft and ctx.needs_input_grad[6]
-        grads = fac.backward(zhats, ctx.lams, ctx.slacks, ctx.nus, dl_dzhat, want=want,
-                             shared=(Q_e, p_e, G_e, h_e, A_e, b_e),
-                             refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0,
-                             dl_dlam=dl_dlam, dl_dnu=dl_dnu if neq > 0 else None, want_dz=want_rho)
+        if torch.is_grad_enabled():
+            # create_graph=True: the same launch inside a node whose backward is the second-order pass
+            unserved = ("with soft rows (rho)" if soft else "with refine > 0 (refine=%d here)" % ctx.refine if ctx.refine > 0
+                        else "on the external-solver path" if ctx.fac is None else None)
+            st = dict(fac=fac, zhat=zhats.detach(), lams=ctx.lams, slacks=ctx.slacks, nus=ctx.nus, want=want,
+                      shared=(Q_e, p_e, G_e, h_e, A_e, b_e), refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0,
+                      want_rho=want_rho, nBatch=nBatch, unserved=unserved)
+            grads = QPBackwardFn.apply(st, dl_dzhat, dl_dlam, dl_dnu if neq > 0 else None, *leaves)
+        else:
+            grads = fac.backward(zhats, ctx.lams, ctx.slacks, ctx.nus, dl_dzhat, want=want,
+                                 shared=(Q_e, p_e, G_e, h_e, A_e, b_e),
+                                 refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0,
+                                 dl_dlam=dl_dlam, dl_dnu=dl_dnu if neq > 0 else None, want_dz=want_rho)
         if want_rho:
             grads, dz = grads[:6], grads[6]
         if neq == 0:
