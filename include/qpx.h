@@ -83,7 +83,8 @@ enum {
     QPX_ST_KKT_BREAKDOWN = 4,  /* factor_kkt failed, best iterate returned  batch.py:110-113 */
     QPX_ST_INACCURATE = 8,     /* best residual > 1 -> INACC_ERR warning   batch.py:141,205  */
     QPX_ST_MAXITER = 16,
-    QPX_ST_NONFINITE = 32
+    QPX_ST_NONFINITE = 32,
+    QPX_ST_NOT_CENTRED = 64    /* qpx_centre ended with its residual above tol (last iterate returned) */
 };
 
 /* stall_policy of qpx_ipm: how `notImprovedLim` (batch.py:127-140, batch-global in the
@@ -336,6 +337,34 @@ int qpx_polish(int dtype, int B, int n, int m, int q,
                const void* A, int64_t sA, const void* b, int64_t sb,
                void* factors, int64_t sfac, int steps, int refine,
                void* zhat, void* nu, void* lam, void* slack, void* best_resid,
+               int32_t* status, qpx_stream_t stream);
+
+/* Additive after v8 (QPX_ABI_VERSION stays 8): CENTRING -- Newton's method onto the point of the central path
+ *   Q z + p + G^T lam + A^T nu = 0,   G z + s = h,   A z = b,   s_i lam_i = kappa_i   (s, lam > 0),
+ * the minimiser of 1/2 z'Qz + p'z - sum_i kappa_i log(h_i - g_i'z) s.t. Az = b, started from the iterate (zhat, nu, lam, slack)
+ * a loop launch returned, its (s, lam) first lifted row by row onto s_i lam_i >= kappa_i from below (s to kappa / lam, then
+ * lam to kappa / s, neither denominator below sqrt(kappa): values only grow, and an entry that came in as 0 or not positive
+ * becomes sqrt(kappa) -- the loop returns s = lam = 0 exactly on a weakly active row of a QP its start point solves).  One kernel, one workgroup per QP, the iterate in float64; per step: the
+ * residuals rx, rz, ry from the caller's Q, p, G, h, A, b in float64 accumulation and rc_i = s_i lam_i - kappa_i, ONE
+ * factorisation of R + diag(s/lam) and ONE solve through the factors of qpx_pre_factor -- solve_kkt(rx, rs, rz, ry) with
+ * rs_i = lam_i - kappa_i / s_i --, the full step where it keeps s, lam > 0, else 0.99 of the step to the boundary.  A QP stops
+ * when  res = max(||rx||_inf, ||rz||_inf, ||ry||_inf, max_i |rc_i| / kappa_i) <= tol  or after max_steps steps.  The four
+ * arrays are overwritten with the LAST iterate, resid (dtype[B], may be NULL) with its res, steps (int32[B], may be NULL) with
+ * the Newton steps taken.  kappa: (B,m) of dtype, batch stride skappa in elements, 0 = one (m) vector for the batch.
+ * status: a kappa entry that is not finite and > 0 ORs QPX_ST_NONFINITE (nothing else is written for that QP but resid =
+ * +inf, steps = 0); a breakdown of a factorisation ORs QPX_ST_KKT_BREAKDOWN and leaves the four arrays as they came in; a QP
+ * that ends with res > tol (NaN included) ORs QPX_ST_NOT_CENTRED.
+ * Served where the finishing stage is one kernel in float64 arithmetic: dtype QPX_F64 and nz+neq+nineq <= 208 under the
+ * default knob (qpx_centre_supported); QPX_F32, QPX_F32_WIDE, the large-QP family: QPX_ERR_UNSUPPORTED.  NULL kappa, tol <= 0
+ * (or NaN), max_steps < 1: QPX_ERR_ARG.  NOT for factors of qpx_pre_factor_soft: the residuals are those of the hard QP.
+ * The derivative entry points serve the centred point as they stand (d = lam / s = kappa / s^2); the gradient with respect to
+ * kappa_i is dz_i / lam_i, dz the inequality block of the backward's KKT solution. */
+int qpx_centre_supported(int dtype, int n, int m, int q);
+int qpx_centre(int dtype, int B, int n, int m, int q,
+               const void* Q, int64_t sQ, const void* p, int64_t sp, const void* G, int64_t sG, const void* h, int64_t sh,
+               const void* A, int64_t sA, const void* b, int64_t sb,
+               void* factors, int64_t sfac, const void* kappa, int64_t skappa, double tol, int max_steps,
+               void* zhat, void* nu, void* lam, void* slack, void* resid, int32_t* steps,
                int32_t* status, qpx_stream_t stream);
 
 /* Batch-MEAN of the gradient of a parameter that the whole batch shares (qp.py:159-177: the reference

@@ -19,6 +19,7 @@ HIP_SO = os.path.join(_HERE, "libqpx_hip.so")
 
 QPX_F32, QPX_F64, QPX_F32_WIDE = 0, 1, 2      # QPX_F32_WIDE: float32 arrays, float64 factors and arithmetic (include/qpx.h)
 ST_Q_NOT_SPD, ST_A_RANK, ST_KKT_BREAKDOWN, ST_INACCURATE, ST_MAXITER, ST_NONFINITE = 1, 2, 4, 8, 16, 32
+ST_NOT_CENTRED = 64                            # qpx_centre ended above its tolerance
 STALL_OFF, STALL_REFERENCE, STALL_FLOOR = 0, 1, 2
 FAMILY_GRID, FAMILY_TILE, FAMILY_BIG = 1, 2, 3
 
@@ -63,6 +64,9 @@ _SIGNATURES = {
     "qpx_polish_supported": (_i, [_i, _i, _i, _i]),
     "qpx_polish": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                         _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qpx_centre_supported": (_i, [_i, _i, _i, _i]),
+    "qpx_centre": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                        _vp, _i64, _vp, _i64, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qpx_batch_outer": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, ctypes.c_size_t, _vp]),
     "qpx_batch_outer_workspace_elems": (ctypes.c_size_t, [_i, _i, _i, _i]),
     "qpx_dense_solve": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -257,6 +261,16 @@ class QpxLib:
             _dtype_code(factors), B, n, m, q, Qp.ptr, Qp.stride, pp.ptr, pp.stride, Gp.ptr, Gp.stride, hp.ptr, hp.stride,
             Ap.ptr, Ap.stride, bp.ptr, bp.stride, _ptr(factors), int(sfac), int(steps), int(refine),
             _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(best_resid), _ptr(status), _stream(factors)))
+
+    # -- Newton's method onto the central-path point s lam = kappa, from a loop launch's iterate
+    def centre(self, B, n, m, q, Q, p, G, h, A, b, factors, sfac, kappa, tol, max_steps, zhat, nu, lam, slack, resid, steps, status):
+        """kappa (B,m) or (m,) / (1,m) (shared: batch stride 0)"""
+        Qp, Gp, Ap = Param(Q, 3), Param(G, 3), Param(A, 3)
+        pp, hp, bp, kp = Param(p, 2), Param(h, 2), Param(b, 2), Param(kappa, 2)
+        self.check(self.dll.qpx_centre(
+            _dtype_code(factors), B, n, m, q, Qp.ptr, Qp.stride, pp.ptr, pp.stride, Gp.ptr, Gp.stride, hp.ptr, hp.stride,
+            Ap.ptr, Ap.stride, bp.ptr, bp.stride, _ptr(factors), int(sfac), kp.ptr, kp.stride, float(tol), int(max_steps),
+            _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(resid), _ptr(steps), _ptr(status), _stream(factors)))
 
     # -- qp.py:159-177, the `.mean(0)` of a shared parameter's gradient as one contraction over the batch
     def batch_outer(self, u, v, w, x, scale, out):

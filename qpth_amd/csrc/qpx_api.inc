@@ -469,6 +469,43 @@ int api_polish(int B, int n, int m, int q, const void* Q, int64_t sQ, const void
     return QPX_ERR_UNSUPPORTED;
 }
 
+// Centring (qpx_centre): the centring role of the one-kernel finishing stage's forms (qpx_forms.h: kPolishCentreRole), float64
+// arithmetic.  Which form serves a size is api_polish's rule; the large-QP family and the float32 kernels have no such role.
+inline bool centre_served(int dtype, int n, int m, int q)
+{
+    if (dtype != QPX_F64 || !use_grid(n, m, q)) return false;
+    const int images = blob_images<double>(n, m, q);
+    if (images == 4) {                       // (a small and a large batch cover both choices of polish_tile_chain)
+        const int nbt = tile_nb(m);
+        return lds_elems_centre_tile(nbt, n, q, polish_tile_chain(nbt, 1)) * sizeof(double) <= lds_budget_bytes() &&
+               lds_elems_centre_tile(nbt, n, q, polish_tile_chain(nbt, 1 << 20)) * sizeof(double) <= lds_budget_bytes();
+    }
+    return images == 3 && grid_nb(m) > 0 && lds_elems_centre_grid(16, grid_nb(m), n, q) * sizeof(double) <= lds_budget_bytes();
+}
+inline int api_centre(PolishArgs<double>& a, void* stream)
+{
+    const int n = a.n, m = a.m, q = a.q;
+    a.images = blob_images<double>(n, m, q);
+    if (a.images == 4) {
+        const int nbt = tile_nb(m);
+        const bool ch = polish_tile_chain(nbt, a.B);
+        const size_t tb = lds_elems_centre_tile(nbt, n, q, ch) * sizeof(double);
+        if (tb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
+#define QPX_PICK(NBL, NW, CH) if (nbt == NBL && ch == CH) return launch_polish_tile<NBL + kPolishCentreRole, NW, CH>(a, tb, stream);
+        QPX_FORMS_POLISH_TILE(QPX_PICK)
+#undef QPX_PICK
+        return QPX_ERR_UNSUPPORTED;
+    }
+    if (a.images != 3) return QPX_ERR_UNSUPPORTED;
+    const int nbg = grid_nb(m);
+    const size_t gb = lds_elems_centre_grid(16, nbg, n, q) * sizeof(double);
+    if (gb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
+#define QPX_PICK(NBL) if (nbg == NBL) return launch_polish_grid<double, NBL + kPolishCentreRole>(a, gb, stream);
+    QPX_FORMS_POLISH_GRID(QPX_PICK)
+#undef QPX_PICK
+    return QPX_ERR_UNSUPPORTED;
+}
+
 template <class T>
 int api_batch_outer(int B, int r, int c, const void* u, const void* v, const void* w, const void* x, double scale,
                     void* out, void* ws, size_t ws_elems, void* stream)
@@ -779,6 +816,32 @@ int qpx_polish(int dtype, int B, int n, int m, int q, const void* Q, int64_t sQ,
     return dtype == QPX_F64
                ? qpx::api_polish<double>(B, n, m, q, Q, sQ, p, sp, G, sG, h, sh, A, sA, b, sb, factors, sfac, steps, refine, zhat, nu, lam, slack, best_resid, status, stream)
                : qpx::api_polish<float>(B, n, m, q, Q, sQ, p, sp, G, sG, h, sh, A, sA, b, sb, factors, sfac, steps, refine, zhat, nu, lam, slack, best_resid, status, stream);
+}
+
+int qpx_centre_supported(int dtype, int n, int m, int q)
+{
+    if (qpx::check_dims(dtype, 1, n, m, q) != QPX_OK) return 0;
+    return qpx::centre_served(dtype, n, m, q) ? 1 : 0;
+}
+
+int qpx_centre(int dtype, int B, int n, int m, int q, const void* Q, int64_t sQ, const void* p, int64_t sp, const void* G,
+               int64_t sG, const void* h, int64_t sh, const void* A, int64_t sA, const void* b, int64_t sb, void* factors,
+               int64_t sfac, const void* kappa, int64_t skappa, double tol, int max_steps, void* zhat, void* nu, void* lam,
+               void* slack, void* resid, int32_t* steps, int32_t* status, qpx_stream_t stream)
+{
+    const int e = qpx::check_dims(dtype, B, n, m, q);
+    if (e) return e;
+    if (!Q || !p || !G || !h || !factors || !zhat || !lam || !slack || (q > 0 && (!A || !b || !nu))) return QPX_ERR_ARG;
+    if (!kappa || skappa < 0 || !(tol > 0.0) || max_steps < 1) return QPX_ERR_ARG;
+    if (!qpx::centre_served(dtype, n, m, q)) return QPX_ERR_UNSUPPORTED;
+    qpx::PolishArgs<double> a{};
+    a.B = B; a.n = n; a.m = m; a.q = q; a.fac = (double*)factors; a.fac_stride = (size_t)sfac;
+    a.Q = (const double*)Q; a.G = (const double*)G; a.A = (const double*)A; a.sQ = sQ; a.sG = sG; a.sA = sA;
+    a.p = (const double*)p; a.h = (const double*)h; a.b = (const double*)b; a.sp = sp; a.sh = sh; a.sb = sb;
+    a.zhat = (double*)zhat; a.nu = (double*)nu; a.lam = (double*)lam; a.slack = (double*)slack;
+    a.steps = max_steps; a.refine = 0; a.best_resid = (double*)resid; a.status = status;
+    a.kappa = (const double*)kappa; a.skappa = skappa; a.tol = tol; a.steps_out = steps;
+    return qpx::api_centre(a, stream);
 }
 
 int qpx_dense_solve(int dtype, int B, int k, void* M, void* rhs, int32_t* status, qpx_stream_t stream)

@@ -41,6 +41,12 @@ constexpr int kKktB2Role = 128;
 // rows' code: their registers are the ones they had without it.
 constexpr int kPrefacSoft = 64;
 
+// Every form of the one-kernel finishing stage exists a second time, float64 arithmetic only, as the CENTRING role
+// (qpx_centre; qpx_grid.h: polish_centre_role): Newton steps onto the central-path point s_i lam_i = kappa_i.  Blocks / tile
+// rows + kPolishCentreRole in the form's FIRST parameter, as above (polish_mat_body decodes it through PolishForm).  The
+// finishing forms hold none of its code.
+constexpr int kPolishCentreRole = 64;
+
 }  // namespace qpx
 
 // thread-grid kernels: (blocks of 16 -- of 8 in the one-wave grid -- per side), (blocks, slots of 64 columns)

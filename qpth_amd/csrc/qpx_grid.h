@@ -2468,12 +2468,243 @@ QPX_DEV void polish_mat_role(const Block& b, const PolishArgs<T>& a, int qp, T* 
     if (b.tid == 0 && a.best_resid) a.best_resid[qp] = (T)sc[kBest];
 }
 
-template <class T, class Mat>
+// The CENTRING role of the finishing-stage forms (qpx_centre, include/qpx.h; forms: first parameter + kPolishCentreRole,
+// float64 arithmetic only): Newton's method onto the central-path point
+//   Q x + p + G^T z + A^T y = 0,   G x + s = h,   A x = b,   s_i z_i = kappa_i        
+// from the iterate a loop launch returned.  The iterate lives in double in LDS and the residuals come from the caller's data,
+// as above; per step ONE factorisation of R + diag(s/z) and ONE un-refined solve_kkt(rx, rs = z - kappa/s, rz, ry) -- the
+// finishing stage's affine solve, without its corrector, step-length heuristics and best-iterate rule: the last iterate is
+// the answer.  Every role of a chain-wave form issues the same barriers (the stop and breakdown flags are block-uniform).
+template <class T, class Mat, class P>
+QPX_DEV void polish_centre_role(const Block& b, const PolishArgs<T>& a, int qp, T* lds, const P& g)
+{
+    static_assert(sizeof(T) == 8, "the centring role is built in float64 arithmetic only");
+    constexpr int M8 = Mat::MP, NT = Mat::NT;
+    const int n = a.n, m = a.m, q = a.q;
+    const FacLayout lay = fac_layout(n, m, q, a.images);
+    T* F = a.fac + (size_t)qp * a.fac_stride;
+    const size_t v = align4(max2(max2((size_t)n, (size_t)M8), (size_t)q));
+    T* rd = lds;
+    T* vD = rd + v;       // s/z (1 on the pad): the diagonal added to R
+    T* vRS = vD + v;      // z - kappa/s
+    T* vRX = vRS + v;     // residuals of the iterate
+    T* vRZ = vRX + v;
+    T* vRY = vRZ + v;
+    T* vRH = vRY + v;     // work vectors of the solve
+    T* vTm = vRH + v;
+    T* vDZ = vTm + v;     // the Newton step
+    T* vDX = vDZ + v;
+    T* vDY = vDX + v;
+    T* vDS = vDY + v;
+    T* xd = vDS + v;      // the iterate
+    T* sd = xd + v;
+    T* zd = sd + v;
+    T* yd = zd + v;
+    T* kp = yd + v;       // kappa (1 on the pad)
+    T* sc = kp + v;       // 16 scalars
+    T* part = sc + 16;    // NT partial sums of the column products (resid_cols_all)
+    T* scr = part + NT;   // Mat::scratch_elems()
+    enum { kRes = 0, kRes0, kStop, kBad, kAlpha };
+
+    const T* Qg = a.Q + (size_t)qp * a.sQ;
+    const T* Gg = a.G + (size_t)qp * a.sG;
+    const T* Ag = (q > 0) ? a.A + (size_t)qp * a.sA : nullptr;
+    const T* pg = a.p + (size_t)qp * a.sp;
+    const T* hg = a.h + (size_t)qp * a.sh;
+    const T* bg = (q > 0) ? a.b + (size_t)qp * a.sb : nullptr;
+    const T* kg = a.kappa + (size_t)qp * a.skappa;
+    int lane = b.lane();
+    const bool w0 = g.lead(b);
+    const double tiny = Lim<double>::tiny();
+
+    for (int i = b.tid; i < (int)v; i += NT) {
+        xd[i] = (i < n) ? a.zhat[(size_t)qp * n + i] : 0.0;
+        sd[i] = (i < m) ? a.slack[(size_t)qp * m + i] : 1.0;
+        zd[i] = (i < m) ? a.lam[(size_t)qp * m + i] : 1.0;
+        yd[i] = (i < q) ? a.nu[(size_t)qp * q + i] : 0.0;
+        kp[i] = (i < m) ? kg[i] : 1.0;
+        vD[i] = vRS[i] = vRX[i] = vRZ[i] = vRY[i] = vRH[i] = vTm[i] = vDZ[i] = vDX[i] = vDY[i] = vDS[i] = 0.0;
+    }
+    if (b.tid == 0) sc[kBad] = sc[kStop] = sc[kRes] = sc[kRes0] = 0.0;
+    Mat::sync(b);
+    if (w0) {
+        bool bad = false;
+        for (int i = lane; i < m; i += kWave) bad = bad || !(kp[i] > 0.0) || !finite_(kp[i]);
+        bad = b.any(bad);
+        if (bad && lane == 0) sc[kBad] = 1.0;
+    }
+    Mat::sync(b);
+    if (sc[kBad] != 0.0) {                                           // uniform: a kappa entry that is not finite and > 0
+        if (b.tid == 0) {
+            if (a.status) a.status[qp] |= QPX_ST_NONFINITE;
+            if (a.best_resid) a.best_resid[qp] = Lim<double>::inf();
+            if (a.steps_out) a.steps_out[qp] = 0;
+        }
+        return;
+    }
+    // The start is lifted onto s_i z_i >= kappa_i from below, row by row: s to kappa / z and then z to kappa / s, neither
+    // denominator below sqrt(kappa).  Values only grow, a pair with s z >= kappa stays as it is, and an entry the loop returned
+    // as exactly 0 (a weakly active row of a QP its start point already solves: s = z = 0) or not positive becomes sqrt(kappa).
+    for (int i = b.tid; i < m; i += NT) {
+        const double k = kp[i], rk = sqrt_(k);
+        double s = (sd[i] > 0.0) ? sd[i] : 0.0, z = (zd[i] > 0.0) ? zd[i] : 0.0;
+        s = max2_(s, k / max2_(z, rk));
+        z = max2_(z, k / max2_(s, rk));
+        sd[i] = s;
+        zd[i] = z;
+    }
+    Mat::sync(b);
+
+    // (the thread index the vector loops and products of a step start from is made opaque once per step: hoisted out of the
+    // Newton loop, their addresses sat in registers through the factorisation)
+    Block bi = b;
+    bool ok = true;
+    auto wgsync = [&]() { Mat::sync(b); };
+    const T* nullT = nullptr;
+    // one application of the condensed KKT inverse with a step's factor E (polish_mat_role::apply)
+    auto apply = [&](const typename Mat::Regs& E, const T* rX, const T* rY, T* rH, T* oZ, T* oX, T* oY) {
+        resid_cols_all<T, T>(bi, NT, rH, rH, m, F + lay.MT, rX, n, nullT, nullT, 0, nullT, nullT, 0, part, wgsync);      // rH += M rX
+        if (q > 0) {
+            for (int j = bi.tid; j < m; j += NT) {
+                T acc = rH[j];
+                for (int r = 0; r < q; ++r) acc = fma_(F[lay.W + (size_t)j * q + r], rY[r], acc);
+                rH[j] = acc;
+            }
+            Mat::sync(b);
+        }
+        Mat::solve_neg(b, g, E, rd, m, rH, oZ, vTm, scr);
+        resid_cols_all<T, T>(bi, NT, oX, nullT, n, F + lay.Kneg, rX, n, nullT, nullT, 0, nullT, nullT, 0, part, wgsync);  // oX = -K rX
+        block_matvec16<T, 2>(bi, oX, F + lay.MT, oZ, n, m);
+        if (q > 0) {
+            Mat::sync(b);
+            block_matTvec<T, 1>(bi, oX, F + lay.NTn, rY, q, n);
+            for (int r = bi.tid; r < q; r += NT) {
+                T acc = 0;
+                for (int c2 = 0; c2 < q; ++c2) acc = fma_(F[lay.S11i + (size_t)r * q + c2], rY[c2], acc);
+                for (int k = 0; k < n; ++k) acc = fma_(F[lay.NTn + (size_t)r * n + k], rX[k], acc);
+                for (int j = 0; j < m; ++j) acc = fma_(-F[lay.W + (size_t)j * q + r], oZ[j], acc);
+                oY[r] = acc;
+            }
+        }
+        Mat::sync(b);
+    };
+    // min over dv < 0 of -v / dv (inf if none), by the lead wave
+    auto step_len = [&](const T* vv, const T* dv) {
+        double al = Lim<double>::inf();
+        for (int i = lane; i < m; i += kWave) {
+            const double d = dv[i];
+            if (d < 0.0) al = min2_(al, -vv[i] / d);
+        }
+        return wave_min(b, al);
+    };
+
+    int st = 0;
+    for (;; ++st) {
+        bi.tid = b.tid;
+        QPX_LAUNDER_V(bi.tid);
+        lane = b.lane();
+        QPX_LAUNDER_V(lane);
+        // ---- residuals of the current iterate (double accumulation) and the stop test
+        resid_cols_all<T, T>(bi, NT, vRX, pg, n, Qg, xd, n, Gg, zd, m, Ag, yd, q, part, wgsync);
+        resid_rows<T, T, T>(bi, vRZ, sd, hg, Gg, xd, m, n, 1.0);
+        if (Ag) resid_rows<T, T, T>(bi, vRY, nullT, bg, Ag, xd, q, n, 1.0);
+        Mat::sync(b);
+        if (w0) {
+            double res = 0.0;
+            auto up = [&](double x) {                                // max with |x|; a NaN counts as +inf
+                x = abs_(x);
+                if (!(x <= res)) res = (x == x) ? x : Lim<double>::inf();
+            };
+            for (int i = lane; i < n; i += kWave) up(vRX[i]);
+            for (int i = lane; i < m; i += kWave) { up(vRZ[i]); up((sd[i] * zd[i] - kp[i]) / kp[i]); }
+            for (int i = lane; i < q; i += kWave) up(vRY[i]);
+            res = wave_max(b, res);
+            b.wave_sync();
+            if (lane == 0) {
+                sc[kRes] = res;
+                if (st == 0) sc[kRes0] = res;
+                sc[kStop] = (res <= a.tol || st >= a.steps) ? 1.0 : 0.0;
+            }
+        }
+        Mat::sync(b);
+        if (sc[kStop] != 0.0) break;                                 // uniform
+        // ---- factor T = R + diag(s/z)
+        for (int i = bi.tid; i < M8; i += NT) {
+            const double s = max2_(sd[i], tiny);
+            vD[i] = (i < m) ? s / max2_(zd[i], tiny) : 1.0;
+            vRS[i] = (i < m) ? zd[i] - kp[i] / s : 0.0;
+        }
+        Mat::sync(b);
+        typename Mat::Regs E;
+        Mat::load(b, g, E, Mat::image(F, lay));
+        Mat::add_diag(g, E, vD);
+        ok = Mat::ldl_inv(b, g, E, scr, rd, m);
+        if (!ok) break;                                              // uniform
+        bi.tid = b.tid;                                              // (again: nothing of the first half stays live through ldl_inv)
+        QPX_LAUNDER_V(bi.tid);
+        lane = b.lane();
+        QPX_LAUNDER_V(lane);
+        // ---- the Newton step: solve_kkt(rx, rs, rz, ry), ds = (-rs - dz) s/z
+        for (int i = bi.tid; i < M8; i += NT) vRH[i] = (i < m) ? vRS[i] * vD[i] - vRZ[i] : 0.0;
+        Mat::sync(b);
+        apply(E, vRX, vRY, vRH, vDZ, vDX, vDY);
+        for (int i = bi.tid; i < M8; i += NT) vDS[i] = (i < m) ? (-vRS[i] - vDZ[i]) * vD[i] : 0.0;
+        Mat::sync(b);
+        // ---- the full step where it keeps s, z > 0, else 0.99 of the step to the boundary
+        if (w0) {
+            double al = min2_(step_len(zd, vDZ), step_len(sd, vDS));
+            al = (al > 1.0) ? 1.0 : 0.99 * al;
+            b.wave_sync();
+            if (lane == 0) sc[kAlpha] = al;
+        }
+        Mat::sync(b);
+        {
+            const double al = sc[kAlpha];
+            for (int i = bi.tid; i < (int)v; i += NT) {
+                if (i < n) xd[i] = fma_(al, vDX[i], xd[i]);
+                if (i < m) { sd[i] = fma_(al, vDS[i], sd[i]); zd[i] = fma_(al, vDZ[i], zd[i]); }
+                if (i < q) yd[i] = fma_(al, vDY[i], yd[i]);
+            }
+        }
+        Mat::sync(b);
+    }
+    if (!ok) {                                                       // the four arrays stay as they came in
+        if (b.tid == 0) {
+            if (a.status) a.status[qp] |= QPX_ST_KKT_BREAKDOWN | QPX_ST_NOT_CENTRED;
+            if (a.best_resid) a.best_resid[qp] = sc[kRes0];
+            if (a.steps_out) a.steps_out[qp] = st;
+        }
+        return;
+    }
+    for (int i = b.tid; i < n; i += NT) a.zhat[(size_t)qp * n + i] = xd[i];
+    for (int i = b.tid; i < m; i += NT) { a.lam[(size_t)qp * m + i] = zd[i]; a.slack[(size_t)qp * m + i] = sd[i]; }
+    for (int i = b.tid; i < q; i += NT) a.nu[(size_t)qp * q + i] = yd[i];
+    if (b.tid == 0) {
+        if (a.best_resid) a.best_resid[qp] = sc[kRes];
+        if (a.steps_out) a.steps_out[qp] = st;
+        if (!(sc[kRes] <= a.tol) && a.status) a.status[qp] |= QPX_ST_NOT_CENTRED;
+    }
+}
+
+// which role a finishing-stage form is: its matrix type with the role taken out of the first parameter (qpx_forms.h:
+// kPolishCentreRole; TileMat: qpx_tile.h)
+template <class Mat> struct PolishForm {
+    static constexpr bool kCentre = false;
+    using type = Mat;
+};
+template <class T, int GS, int NBL> struct PolishForm<GridMat<T, GS, NBL>> {
+    static constexpr bool kCentre = NBL >= kPolishCentreRole;
+    using type = GridMat<T, GS, (kCentre ? NBL - kPolishCentreRole : NBL)>;
+};
+
+template <class T, class MatF>
 QPX_DEV void polish_mat_body(const Block& b, const PolishArgs<T>& a, int qp, T* lds)
 {
+    using Mat = typename PolishForm<MatF>::type;
     typename Mat::Pos g(b);
     g.assign(b, reinterpret_cast<int*>(lds));
-    Mat::with_role(g, [&](const auto& gp) { polish_mat_role<T, Mat>(b, a, qp, lds, gp); });
+    if constexpr (PolishForm<MatF>::kCentre) Mat::with_role(g, [&](const auto& gp) { polish_centre_role<T, Mat>(b, a, qp, lds, gp); });
+    else Mat::with_role(g, [&](const auto& gp) { polish_mat_role<T, Mat>(b, a, qp, lds, gp); });
 }
 
 template <class T, int GS, int NBL>
@@ -2493,6 +2724,18 @@ QPX_LAYOUT_HD size_t lds_elems_polish_grid(int gs, int nbl, int n, int q, size_t
 {
     const size_t mg = (size_t)gs * nbl;
     return lds_elems_polish_mat(mg, 2 * mg + 4 + (size_t)nbl * gs * gs, n, q, tsize);
+}
+
+// ... of its centring role (polish_centre_role, doubles): 17 vectors, 16 scalars, 256 partial sums, the scratch
+QPX_LAYOUT_HD size_t lds_elems_centre_mat(size_t mp, size_t scratch, int n, int q)
+{
+    const size_t v = align4(max2(max2((size_t)n, mp), (size_t)q));
+    return 17 * v + 16 + 256 + scratch;
+}
+QPX_LAYOUT_HD size_t lds_elems_centre_grid(int gs, int nbl, int n, int q)
+{
+    const size_t mg = (size_t)gs * nbl;
+    return lds_elems_centre_mat(mg, 2 * mg + 4 + (size_t)nbl * gs * gs, n, q);
 }
 
 // LDS elements of the KKT-solve / backward kernel: 12 vectors + the matrix operations' scratch

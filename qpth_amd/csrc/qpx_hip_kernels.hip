@@ -120,6 +120,11 @@ template <class T, int NBL> int launch_polish_grid(const PolishArgs<T>& a, size_
 }
 #define QPX_INSTP(NBL) template int launch_polish_grid<QPX_TU_REAL, NBL>(const PolishArgs<QPX_TU_REAL>&, size_t, void*);
 QPX_FORMS_POLISH_GRID(QPX_INSTP)
+#if QPX_REAL_IS_DOUBLE
+// (NBL + kPolishCentreRole: the form's centring role, qpx_centre -- float64 arithmetic only)
+#define QPX_INSTPC(NBL) template int launch_polish_grid<double, kPolishCentreRole + NBL>(const PolishArgs<double>&, size_t, void*);
+QPX_FORMS_POLISH_GRID(QPX_INSTPC)
+#endif
 #elif QPX_TU_KERNEL == 8
 template <class T, int NBL, int NS> __global__ __launch_bounds__(64) void k_ipm_grid8(IpmArgs<T> a)
 {
@@ -145,7 +150,8 @@ template <int NBL, int NW, bool CH> int launch_polish_tile(const PolishArgs<doub
 {
     return launch_kernel<k_polish_tile<NBL, NW, CH>>(dim3(a.B), 64 * NW, lds_bytes, stream, a);
 }
-#define QPX_INST(NBL, NW, CH) template int launch_polish_tile<NBL, NW, CH>(const PolishArgs<double>&, size_t, void*);
+#define QPX_INST(NBL, NW, CH) template int launch_polish_tile<NBL, NW, CH>(const PolishArgs<double>&, size_t, void*); \
+                              template int launch_polish_tile<NBL + kPolishCentreRole, NW, CH>(const PolishArgs<double>&, size_t, void*);      // (and its centring role, qpx_centre)
 QPX_FORMS_POLISH_TILE(QPX_INST)
 #elif QPX_TU_KERNEL == 14
 // pre_factor_kkt on matrix-core tiles (qpx_prefac.h), f64, neq = 0: four waves per QP, two QPs per CU

@@ -219,6 +219,12 @@ template <class T> struct PolishArgs {
     int steps, refine;
     T* best_resid;                        // out, may be NULL: the reference's residual of the returned iterate (batch.py:103-107)
     int* status;
+    // the centring role (qpx_centre, polish_centre_role; kPolishCentreRole forms only): kappa (B,m), batch stride skappa
+    // (0 = shared); `steps` is max_steps, best_resid the stop test's residual of the returned iterate; steps_out (B), may be NULL
+    const T* kappa = nullptr;
+    long long skappa = 0;
+    double tol = 0.0;
+    int* steps_out = nullptr;
 };
 
 constexpr size_t kMaxLdsBytes = 160 * 1024;   // gfx950: 160 KiB of LDS per workgroup

@@ -162,7 +162,8 @@ enum : int {
     QPX_ST_KKT_BREAKDOWN = 4, // factor_kkt broke down during the IPM loop (best iterate returned)
     QPX_ST_INACCURATE = 8,    // best residual > 1                 -> INACC_ERR warning
     QPX_ST_MAXITER = 16,      // loop ended on maxIter
-    QPX_ST_NONFINITE = 32     // iterate went NaN/Inf (best iterate returned)
+    QPX_ST_NONFINITE = 32,    // iterate went NaN/Inf (best iterate returned)
+    QPX_ST_NOT_CENTRED = 64   // qpx_centre ended above its tolerance (the last iterate is returned)
 };
 
 }  // namespace qpx

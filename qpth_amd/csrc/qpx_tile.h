@@ -1340,6 +1340,16 @@ QPX_DEV void kkt_tile_body(const Block& b, const KktArgs<double>& a, int qp, dou
     else kkt_mat_body<double, TileMat<NBL, NW, CH>, kBackward>(b, a, qp, lds);
 }
 
+// the finishing stage's tile forms: tile rows + kPolishCentreRole is the form's centring role (qpx_grid.h: polish_mat_body)
+template <int NBL, int NW, bool CH> struct PolishForm<TileMat<NBL, NW, CH>> {
+    static constexpr bool kCentre = NBL >= kPolishCentreRole;
+    using type = TileMat<(kCentre ? NBL - kPolishCentreRole : NBL), NW, CH>;
+};
+QPX_LAYOUT_HD size_t lds_elems_centre_tile(int nbl, int n, int q, bool chain)
+{
+    return lds_elems_centre_mat(16 * (size_t)nbl, tile_scratch_elems(nbl, chain ? 3 : 1, chain), n, q);
+}
+
 template <int NBL, int NW, int NS, bool CH = false>
 QPX_DEV void ipm_tile_body(const Block& b, const IpmArgs<double>& a, int qp, double* lds)
 {

@@ -33,7 +33,8 @@ def default_stall_policy(B):
 
 
 class IpmResult:
-    __slots__ = ("zhat", "nu", "lam", "slacks", "iters", "status", "best_resid", "trace", "_warm_used")
+    __slots__ = ("zhat", "nu", "lam", "slacks", "iters", "status", "best_resid", "trace", "_warm_used",
+                 "centre_resid", "centre_steps")         # the last two: set by KKTFactors.centre only
 
     @property
     def warm_used(self):
@@ -103,6 +104,20 @@ def as_rho(rho, Q, nineq, nBatch=1):
     if rho.dim() > 2 or (rho.dim() >= 1 and rho.size(-1) != nineq) or (rho.dim() == 2 and nBatch > 1 and rho.size(0) != nBatch):
         raise ValueError("qpth_amd: rho has shape %s; expected (nBatch, %d), (%d,) or ()" % (tuple(rho.shape), nineq, nineq))
     return rho
+
+
+def as_kappa(kappa, Q, nineq, nBatch=1):
+    """The barrier weights of the smoothed QP as every entry point takes them, as as_rho: a tensor of Q's dtype
+    and device, shape (nBatch, nineq), (nineq,) or (), or a Python number (-> a 0-dim tensor).  Raises ValueError otherwise;
+    the VALUES (finite, > 0) are checked by the centring kernel."""
+    if not torch.is_tensor(kappa):
+        kappa = torch.tensor(float(kappa), dtype=Q.dtype, device=Q.device)
+    if kappa.dtype != Q.dtype or kappa.device != Q.device:
+        raise ValueError("qpth_amd: kappa is %s on %s, the QP is %s on %s" % (kappa.dtype, kappa.device, Q.dtype, Q.device))
+    if (kappa.dim() > 2 or (kappa.dim() >= 1 and kappa.size(-1) != nineq)
+            or (kappa.dim() == 2 and nBatch > 1 and kappa.size(0) != nBatch)):
+        raise ValueError("qpth_amd: kappa has shape %s; expected (nBatch, %d), (%d,) or ()" % (tuple(kappa.shape), nineq, nineq))
+    return kappa
 
 
 class _PinnedPool:
@@ -491,6 +506,48 @@ a non-zero diagonal.
                            "under the current knob -- nz = %d, nineq = %d, neq = %d; it is served up to 512 per dimension "
                            "(qpx_polish_supported).  float32 tensors run in float64 arithmetic by default (refine=None)"
                            % (self.n, self.m, self.q))
+
+    # -- the central-path point at a given kappa ------------------------------------------
+    def centre_ok(self):
+        """does qpx_centre serve these factors (under the knob they were built with)?  float64 tensors, the thread-grid /
+        tile kernels' sizes (nz+neq+nineq <= 208), no soft rows"""
+        if self.soft or self.wide or self.dtype != torch.float64 or not hasattr(self.lib.dll, "qpx_centre_supported"):
+            return False
+        with self._knob():
+            return bool(self.lib.dll.qpx_centre_supported(_lib.QPX_F64, self.n, self.m, self.q))
+
+    def centre(self, p, h, b, res, kappa, tol=1e-9, max_steps=20):
+        """Newton's method from the loop's result `res` onto the point of the central path
+            Q z + p + G'lam + A'nu = 0,  G z + s = h,  A z = b,  s_i lam_i = kappa_i   (s, lam > 0)
+        -- one launch (qpx_centre), no host sync: per step the residuals of the caller's data, one factorisation and one
+        solve; a QP stops at max(|rx|, |rz|, |ry|, |s lam - kappa| / kappa) <= tol (max norms) or after max_steps steps.
+        kappa: (B, nineq), (1, nineq) or (nineq,), every entry finite and > 0 (else QPX_ST_NONFINITE in `status`).  Returns
+        `res`, its zhat, nu, lam, slacks overwritten, with `centre_resid` (B,) and `centre_steps` int32 (B,) added; a QP that
+        ends above tol has _lib.ST_NOT_CENTRED in `res.status`.  backward, jvp, backward2 and solve_kkt_many serve the centred
+        point as they stand; d loss / d kappa = dz / lam, dz of backward(want_dz=True)."""
+        if self.soft:
+            raise ValueError("qpth_amd: no centring (qpx_centre) on factors with soft rows (w / rho): its steps evaluate the "
+                             "residuals of the hard QP")
+        if not self.centre_ok():
+            raise ValueError("qpth_amd: centring (qpx_centre, kappa) is served for float64 tensors up to nz + neq + nineq = 208 "
+                             "under the default knob; got %s, nz = %d, nineq = %d, neq = %d"
+                             % (str(self.dtype).replace("torch.", "") + (" in float64 arithmetic" if self.wide else ""),
+                                self.n, self.m, self.q))
+        B, n, m, q = self.B, self.n, self.m, self.q
+        self._check(p, n, "p")
+        self._check(h, m, "h")
+        if q:
+            self._check(b, q, "b")
+        self._check(kappa, m, "kappa")
+        for name in ("zhat", "lam", "slacks") + (("nu",) if q else ()):
+            setattr(res, name, getattr(res, name).contiguous())
+        res.centre_resid = torch.empty(B, dtype=self.dtype, device=self.device)
+        res.centre_steps = torch.empty(B, dtype=torch.int32, device=self.device)
+        with self._knob():
+            self.lib.centre(B, n, m, q, self.Q, p, self.G, h, self.A if q else None, b if q else None, self.blob, self.sfac,
+                            kappa, tol, max_steps, res.zhat, res.nu if q else None, res.lam, res.slacks,
+                            res.centre_resid, res.centre_steps, self.status)
+        return res
 
     # -- QPFunctionFn.jvp: forward mode ---------------------------------------------------------
     def jvp(self, zhat, lam, slacks, nu, tangents, refine=0, want_duals=False):

@@ -15,6 +15,8 @@ QPFunction(warm_start=ws) starts the loop at the previous call's (lam, slacks) k
 QPFunction(...)(Q, p, G, h, A, b, rho) softens rows of G z <= h by a quadratic penalty, differentiable in rho too.
 The backward is itself differentiable once: torch.autograd.grad(..., create_graph=True) and a second grad give Hessian-vector
 products through the layer, one more launch with one factorisation and two solves (qpx_backward2).
+QPFunction(...)(Q, p, G, h, A, b, kappa=kappa) returns the point of the CENTRAL PATH at kappa instead of the solution -- the
+log-barrier smoothing of the QP, C-infinity in all parameters and in kappa; one more launch in the forward (qpx_centre).
 """
 from enum import Enum
 
@@ -23,7 +25,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .kkt import KKTFactors, as_rho
+from .kkt import KKTFactors, as_kappa, as_rho
 from .solvers.pdipm import batch as pdipm_b
 from .util import expandParam, extract_nBatch
 
@@ -56,9 +58,27 @@ def f64_arithmetic_serves(nz, nineq, neq, lib=None):
 
 def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                maxIter=20, solver=QPSolvers.PDIPM_BATCHED,
-               check_Q_spd=True, refine=None, duals=False, warm_start=None):
-    """Returns f(Q, p, G, h, A, b, rho=None).  `refine`, `duals`, `warm_start` and the seventh input `rho` are what the reference
-    does not have.
+               check_Q_spd=True, refine=None, duals=False, warm_start=None, kappa_tol=1e-9, kappa_steps=20):
+    """Returns f(Q, p, G, h, A, b, rho=None, kappa=None).  `refine`, `duals`, `warm_start` and the inputs `rho` and `kappa` are what
+    the reference does not have.
+    kappa: the barrier-smoothed QP.  The call returns the point of the central path
+          Q z + p + G'lam + A'nu = 0,  G z + s = h,  A z = b,  s_i lam_i = kappa_i   (s, lam > 0),
+      the minimiser of 1/2 z'Qz + p'z - sum_i kappa_i log(h_i - g_i'z) s.t. Az = b, instead of the QP's solution: smooth in all
+      parameters (no kinks, strict complementarity by construction, d = lam / s = kappa / s^2 well conditioned), and kappa -> 0
+      recovers the hard QP.  A tensor of the other inputs' dtype and device, shape (nBatch, nineq), (nineq,) (shared by the
+      batch) or () (one weight for every row), or a Python float; every entry finite and > 0, else ValueError("kappa must be
+      positive") from the forward.  The forward is pre-factorisation, the PDIPM loop and one centring launch (Newton steps
+      until max(|rx|, |rz|, |ry|, |s lam - kappa| / kappa) <= kappa_tol in max norms, kappa_steps at most; a QP that ends
+      above kappa_tol prints one warning line when verbose >= 0).  With a Python float the loop runs to the tolerance
+      max(eps, nineq * kappa) -- it stops about where mu reaches kappa, fewer iterations than the hard call; with a tensor it
+      runs to the caller's eps: pass eps = nineq * kappa.min() to save those iterations.  kappa is a seventh differentiable
+      input in reverse and in forward mode (d loss / d kappa_i = dz_i / lam_i, dz the inequality block of the backward's KKT
+      solution); a shared kappa gets the `.mean(0)` convention, a scalar is summed over the rows as well.  duals=True,
+      warm_start (the holder takes the centred lam, slacks) and second derivatives through create_graph=True work as for
+      the hard QP -- with respect to the six parameters and the cotangents; the second-order gradient with respect to kappa
+      itself is not offered (None), and the first-order gradient of kappa carries no graph.  float64 inputs at sizes the
+      thread-grid / tile kernels serve (nz+neq+nineq <= 208) only; not together with rho, refine > 0, float32 inputs or
+      solver=QPSolvers.CVXPY: each a ValueError from the call.  kappa=None is the call as before: the same nodes and launches.
     Second derivatives: under torch.autograd.grad(..., create_graph=True) the gradients carry a graph, and a second
       grad -- Hessian-vector products, gradient penalties, losses on -dE/dx, MAML-style outer loops -- runs the second-order
       pass: gradients flow to the first backward's cotangents (dl/dzhat, and dl/dlam, dl/dnu under duals=True) and to Q, p,
@@ -107,10 +127,12 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
     Memory: with refine=None a float32 batch in the large-QP family keeps a float64 factor blob (9.4 MB per QP at
     nz = nineq = 500, twice the float32 family's); a batch that only fits HBM with float32 factors should pass refine=2
     (float32 kernels + finishing iterations) or refine=0 explicitly."""
-    def _forward(ctx, Q_, p_, G_, h_, A_, b_, rho_=None):
+    def _forward(ctx, Q_, p_, G_, h_, A_, b_, rho_=None, kappa_=None, loop_eps=None):
         nBatch = extract_nBatch(Q_, p_, G_, h_, A_, b_)
         if rho_ is not None and rho_.dim() == 2:
             nBatch = max(nBatch, rho_.size(0))
+        if kappa_ is not None and kappa_.dim() == 2:
+            nBatch = max(nBatch, kappa_.size(0))
         nineq, nz = G_.size(-2), G_.size(-1)
         neq = A_.size(-2) if A_.nelement() > 0 else 0
         # float32 data, float64 arithmetic (see QPFunction.__doc__)
@@ -140,10 +162,15 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         if solver == QPSolvers.PDIPM_BATCHED:
             fac = KKTFactors.build(Q, G, A, nBatch, wide=ctx.wide, w=w)   # qp.py:93
             warm = warm_start.pair(nBatch, nineq, Q.dtype, Q.device) if warm_start is not None else None
-            res = fac.ipm(p, h, b, eps, maxIter, notImprovedLim,
+            res = fac.ipm(p, h, b, eps if loop_eps is None else loop_eps, maxIter, notImprovedLim,
                           want_trace=(verbose == 1), warm=warm,
                           warm_floor=warm_start.floor if warm is not None else 1e-2)   # qp.py:94-96
             ctx.refine = (2 if Q.dtype == torch.float32 and not ctx.wide else 0) if refine is None else int(refine)
+            if kappa_ is not None:
+                # the smoothed QP: from the loop's iterate onto the central path at kappa, one more launch; ctx
+                # keeps nothing of kappa but its rank: the derivatives read the centred (lam, slacks)
+                kap = kappa_.detach().expand(nineq).unsqueeze(0) if kappa_.dim() < 2 else kappa_.detach()
+                res = fac.centre(p, h, b, res, kap, tol=kappa_tol, max_steps=kappa_steps)
             if ctx.refine > 0:
                 # (the solves inside a finishing step are NOT refined: the step's own residuals are exact, and refining
                 # the directions as well changes nothing in the answer -- C2 / C3 float32, two steps: the same error
@@ -155,7 +182,17 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             fac.raise_on_failure(check_Q_spd)
             if verbose == 1:
                 _print_trace(res)
-            if verbose >= 0:
+            if kappa_ is not None:
+                # one small read-back: a QP the kernel left untouched (resid = inf after 0 steps) had a bad kappa entry
+                bad = ((res.centre_steps == 0) & torch.isinf(res.centre_resid)).any()
+                off = ((res.status & _lib.ST_NOT_CENTRED) != 0).any()
+                bad, off = torch.stack([bad, off]).tolist()
+                if bad:
+                    raise ValueError("kappa must be positive")
+                if off and verbose >= 0:
+                    print("qpth_amd warning: centring ended above kappa_tol = %g for some QPs (worst residual %.3e after at most "
+                          "%d steps); raise kappa_steps" % (kappa_tol, float(res.centre_resid.max().item()), kappa_steps))
+            elif verbose >= 0:
                 if not bool((res.best_resid <= 1.).all().item()):
                     print(pdipm_b.INACC_ERR)                     # batch.py:141-142,205-206
             ctx.fac = fac
@@ -173,6 +210,7 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         # which runs inside this very call, reads ctx.rho)
         ctx.save_for_backward(zhats, Q_, p_, G_, h_, A_, b_, *(() if rho_ is None else (rho_,)))
         ctx.rho_dim = None if rho_ is None else rho_.dim()
+        ctx.kappa_dim = None if kappa_ is None else kappa_.dim()
         # forward mode reads no saved_tensors: zhat as an attribute beside lam, s, nu (detached: no cycle through the
         # output's grad_fn), and on the external-solver path the matrices the factors are rebuilt from
         ctx.zhat = zhats.detach()
@@ -190,7 +228,7 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             ctx.mark_non_differentiable(slacks)
         return zhats, nus, lams, slacks
 
-    def _jvp(ctx, dQ, dp, dG, dh, dA, db, drho=None):
+    def _jvp(ctx, dQ, dp, dG, dh, dA, db, drho=None, dkappa=None):
         # forward mode: z' solves the backward's KKT system (same d, same factors) with the right-hand side formed from
         # the tangents on the device -- one launch, no host sync.  A None / empty tangent is zero.
         fac = ctx.fac
@@ -203,6 +241,10 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             # w = 1 / rho enters the KKT rows like h times lam (G z - w lam + s = h): th + tw lam, tw = -trho / rho^2
             tw = -drho / (ctx.rho * ctx.rho)
             dh = tw * ctx.lams if dh is None else dh + tw * ctx.lams
+        if dkappa is not None:
+            # s lam = kappa linearised, divided by lam: the tangent of kappa enters the rows G z + s = h like -tkappa / lam on h
+            th = -dkappa / ctx.lams
+            dh = th if dh is None else dh + th
         if not duals:
             return fac.jvp(ctx.zhat, ctx.lams, ctx.slacks, ctx.nus, (dQ, dp, dG, dh, dA, db), refine=rf)
         # (z', nu', lam') from the same single launch; the slacks carry no tangent (non-differentiable)
@@ -253,8 +295,9 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         b, b_e = expandParam(b, nBatch, 2)
         neq = ctx.neq
         soft = ctx.rho_dim is not None
+        smooth = ctx.kappa_dim is not None
         if dl_dzhat is None and dl_dlam is None and (dl_dnu is None or neq == 0):
-            return (None,) * (7 if soft else 6)                  # duals=True and no cotangent on any differentiable output
+            return (None,) * (7 if soft else 8 if smooth else 6)     # duals=True and no cotangent on any differentiable output
 
         fac = ctx.fac
         if fac is None:                                          # qp.py:142-143
@@ -268,7 +311,7 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         # (qp.py:159-177) is taken inside KKTFactors.backward -- for Q, G, A as one contraction over
         # the batch instead of nBatch outer products.
         want = tuple(ctx.needs_input_grad[:6])
-        want_rho = soft and ctx.needs_input_grad[6]
+        want_rho = (soft or smooth) and ctx.needs_input_grad[6]     # (rho's gradient or kappa's: both read dz of the KKT solution)
         if torch.is_grad_enabled():
             # create_graph=True: the same launch inside a node whose backward is the second-order pass
             unserved = ("with soft rows (rho)" if soft else "with refine > 0 (refine=%d here)" % ctx.refine if ctx.refine > 0
@@ -286,6 +329,17 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             grads, dz = grads[:6], grads[6]
         if neq == 0:
             grads = grads[:4] + (None, None)
+        if smooth:
+            dkappa = None
+            if want_rho:
+                # d loss / d kappa = dz / lam, reduced like drho; it carries no graph (second derivatives with respect
+                # to kappa are not offered)
+                dkappa = dz.detach() / ctx.lams
+                if ctx.kappa_dim < 2:
+                    dkappa = dkappa.mean(0)
+                if ctx.kappa_dim == 0:
+                    dkappa = dkappa.sum()
+            return grads + (dkappa, None)
         if not soft:
             return grads
         drho = None
@@ -327,7 +381,46 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         def backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
             return _backward(ctx, dl_dzhat, dl_dnu, dl_dlam, dl_dslacks)
 
-    def apply(Q, p, G, h, A, b, rho=None):
+    class QPSmoothFunctionFn(Function):
+        """the node of the barrier-smoothed QP: kappa, the seventh differentiable input, behind the six parameters (and the loop's
+        tolerance, a Python float or None, which is no tensor and gets no gradient)"""
+        @staticmethod
+        def forward(ctx, Q_, p_, G_, h_, A_, b_, kappa_, loop_eps):
+            return _forward(ctx, Q_, p_, G_, h_, A_, b_, None, kappa_, loop_eps)
+
+        @staticmethod
+        def jvp(ctx, dQ, dp, dG, dh, dA, db, dkappa, _):
+            return _jvp(ctx, dQ, dp, dG, dh, dA, db, None, dkappa)
+
+        @staticmethod
+        def backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
+            return _backward(ctx, dl_dzhat, dl_dnu, dl_dlam, dl_dslacks)
+
+    def _apply_smooth(Q, p, G, h, A, b, rho, kappa):
+        what = "qpth_amd: kappa (the barrier-smoothed QP)"
+        if rho is not None:
+            raise ValueError(what + " together with rho (soft rows) is not served: the centring steps evaluate the residuals of "
+                             "the hard QP")
+        if solver != QPSolvers.PDIPM_BATCHED:
+            raise ValueError(what + " is served by solver=QPSolvers.PDIPM_BATCHED only")
+        if refine is not None and int(refine) > 0:
+            raise ValueError(what + " with refine=%d: the centring launch already iterates on the residuals of the caller's data; "
+                             "pass refine=0 or refine=None" % int(refine))
+        if Q.dtype != torch.float64:
+            raise ValueError(what + " is served for float64 inputs only (the centring kernel exists in float64 arithmetic), "
+                             "got %s" % Q.dtype)
+        nineq, nz = G.size(-2), G.size(-1)
+        neq = A.size(-2) if A.nelement() > 0 else 0
+        if not _lib.backend_for(Q).dll.qpx_centre_supported(_lib.QPX_F64, nz, nineq, neq):
+            raise ValueError(what + " is served up to nz + neq + nineq = 208 (the thread-grid / tile kernels, "
+                             "qpx_centre_supported); got nz = %d, nineq = %d, neq = %d" % (nz, nineq, neq))
+        loop_eps = None if torch.is_tensor(kappa) else max(float(eps), nineq * float(kappa))
+        kappa = as_kappa(kappa, Q, nineq, extract_nBatch(Q, p, G, h, A, b))
+        return QPSmoothFunctionFn.apply(Q, p, G, h, A, b, kappa, loop_eps)
+
+    def apply(Q, p, G, h, A, b, rho=None, kappa=None):
+        if kappa is not None:
+            return _apply_smooth(Q, p, G, h, A, b, rho, kappa)
         if rho is None:
             return QPFunctionFn.apply(Q, p, G, h, A, b)
         if solver != QPSolvers.PDIPM_BATCHED:

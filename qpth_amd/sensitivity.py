@@ -15,7 +15,7 @@ An analysis interface, not an autograd node: every output is detached, and `QPFu
 import torch
 
 from . import _lib
-from .kkt import KKTFactors, as_rho
+from .kkt import KKTFactors, as_kappa, as_rho
 from .qp import _print_trace, f64_arithmetic_serves
 from .solvers.pdipm import batch as pdipm_b
 from .util import expandParam, extract_nBatch
@@ -131,7 +131,8 @@ class QPSolution:
         return J
 
 
-def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd=True, verbose=-1, warm_start=None, rho=None):
+def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd=True, verbose=-1, warm_start=None, rho=None,
+          kappa=None, kappa_tol=1e-9, kappa_steps=20):
     """The forward of QPFunction(eps, verbose, notImprovedLim, maxIter, check_Q_spd)(Q, p, G, h, A, b) with its defaults for
     float32 (float64 arithmetic where f64_arithmetic_serves, else the float32 kernels + two finishing steps): un-batched
     parameters are broadcast, a Q that is not SPD raises.  Returns the QPSolution; nothing is recorded for autograd.
@@ -140,7 +141,11 @@ def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd
     rho: soft inequality rows, as the seventh input of QPFunction's callable: (nBatch, nineq), (nineq,), () or a
     float, > 0, +inf = a hard row.  vjp_many(want=(..., "rho")) and jacobian(wrt=(..., "rho")) then differentiate in it.
     float32 inputs need a size that runs in float64 arithmetic (f64_arithmetic_serves): the finishing steps of the other
-    sizes evaluate residuals of the hard QP."""
+    sizes evaluate residuals of the hard QP.
+    kappa: the barrier-smoothed QP, as QPFunction's `kappa`: (nBatch, nineq), (nineq,), () or a float, > 0.  The
+    iterate is centred onto the central path at kappa (KKTFactors.centre, to kappa_tol in kappa_steps steps at most) before the
+    state is kept, so jacobian() and vjp_many() are those of the smoothed map.  float64 inputs up to nz+neq+nineq = 208, not
+    together with rho (ValueError)."""
     with torch.no_grad():
         nBatch = extract_nBatch(Q, p, G, h, A, b)
         nineq, nz = G.size(-2), G.size(-1)
@@ -156,6 +161,16 @@ def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd
             rho_dim = rho.dim()
             rho = rho.detach().expand(nineq).unsqueeze(0) if rho_dim < 2 else rho.detach()
             nBatch = max(nBatch, rho.size(0))
+        if kappa is not None:
+            if rho is not None:
+                raise ValueError("qpth_amd: kappa (the barrier-smoothed QP) together with rho (soft rows) is not served")
+            if Q.dtype != torch.float64:
+                raise ValueError("qpth_amd: kappa (the barrier-smoothed QP) is served for float64 inputs only, got %s" % Q.dtype)
+            loop_eps = None if torch.is_tensor(kappa) else max(float(eps), nineq * float(kappa))
+            kappa = as_kappa(kappa, Q, nineq, nBatch).detach()
+            kappa = kappa.expand(nineq).unsqueeze(0) if kappa.dim() < 2 else kappa
+            nBatch = max(nBatch, kappa.size(0))
+            eps = eps if loop_eps is None else loop_eps
         params, shared = zip(*[expandParam(X.detach(), nBatch, nd) for X, nd in zip((Q, p, G, h, A, b), (3, 2, 3, 2, 3, 2))])
         Qe, pe, Ge, he, Ae, be = params
         fac = KKTFactors.build(Qe, Ge, Ae, nBatch, wide=wide, w=None if rho is None else rho.reciprocal())
@@ -165,11 +180,16 @@ def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd
         refine = 2 if (Q.dtype == torch.float32 and not wide) else 0
         if refine > 0:
             res = fac.polish(pe, he, be, res, steps=refine, refine=0)
+        if kappa is not None:
+            res = fac.centre(pe, he, be, res, kappa, tol=kappa_tol, max_steps=kappa_steps)      # (refuses unserved sizes)
         if warm_start is not None:
             warm_start.take(res)
         fac.raise_on_failure(check_Q_spd)
         if verbose == 1:
             _print_trace(res)
-        if verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
+        if kappa is not None:
+            if bool(((res.centre_steps == 0) & torch.isinf(res.centre_resid)).any().item()):
+                raise ValueError("kappa must be positive")
+        elif verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
             print(pdipm_b.INACC_ERR)
         return QPSolution(fac, res, params, shared, refine, rho, rho_dim)
