@@ -367,6 +367,38 @@ int qpx_centre(int dtype, int B, int n, int m, int q,
                void* zhat, void* nu, void* lam, void* slack, void* resid, int32_t* steps,
                int32_t* status, qpx_stream_t stream);
 
+/* Additive after v8 (QPX_ABI_VERSION stays 8): TWO-SIDED inequality rows,  lower <= G z <= h  in nineq rows --
+ * the QP a caller had to write as [G; -G] z <= [h; -lower] with 2 nineq rows.  The factors are those of qpx_pre_factor for
+ * (Q, G, A): the doubled QP's Newton system collapses to the m x m system the loop already factors, with the diagonal
+ * 1/(zu/su + zl/sl); the iterates, iteration counts and stop rule are those of qpx_ipm on the doubled QP.
+ * qpx_ipm_range: qpx_ipm's arguments, then
+ *   lower (B,m) of dtype, batch stride slo in elements (0 = one (m) vector for the batch); -inf = a ONE-SIDED row, as in qpx_ipm;
+ *   gt1 (B) of dtype: || G^T e ||_2 per QP, e_i = 1 on the one-sided rows and 0 on the two-sided ones -- the doubled QP's
+ *     || G'^T 1 || of the stop rule (batch.py:103-107) --, NULL = 0 (every row two-sided);
+ *   lam_lo, slack_lo (B,m) of dtype, out: the multipliers and slacks of the rows  lower <= G z  beside lam, slack of  G z <= h;
+ *     0 and +inf on a one-sided row.
+ * status: a lower entry that is NaN, +inf or not below its h ORs QPX_ST_NONFINITE and the QP is left as after a failed
+ * pre-factorisation: NaN in the outputs, iters = 0, best_resid = +inf.  trace as in qpx_ipm; mu is the doubled QP's (over
+ * nineq + the number of two-sided rows).
+ * qpx_backward_range: qpx_backward's arguments, then lam_lo, slack_lo (B,m) as qpx_ipm_range wrote them.  One launch: the
+ * backward's KKT solve with d = clamp(lam)/clamp(slack) + clamp(lam_lo)/clamp(slack_lo) and lam - lam_lo where lam meets dx
+ * in dG.  dz is v = dz_upper - dz_lower of the doubled QP's solution; the gradients with respect to the two bounds are
+ *   dl/dh = -v du/(du + dl),   dl/dlower = -v dl/(du + dl),   du = clamp(lam)/clamp(slack), dl = clamp(lam_lo)/clamp(slack_lo)
+ * (exactly 0 on a one-sided row), which the caller forms from dz; dh, if given, receives their sum -v.  refine must be 0.
+ * Served in float64 arithmetic by the loop and backward forms the default dispatch picks, nz+neq+nineq <= 208
+ * (qpx_range_supported); QPX_F32, QPX_F32_WIDE, the large-QP family and forms reachable through the A/B knob alone:
+ * QPX_ERR_UNSUPPORTED.  No warm start, no soft factors (qpx_pre_factor_soft) and no refinement in this role. */
+int qpx_range_supported(int dtype, int n, int m, int q);
+int qpx_ipm_range(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
+                  const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
+                  int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
+                  void* best_resid, void* trace, const void* lower, int64_t slo, const void* gt1, void* lam_lo,
+                  void* slack_lo, qpx_stream_t stream);
+int qpx_backward_range(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat, const void* lam,
+                       const void* slack, const void* nu, const void* dl_dz, void* dQ, void* dp, void* dG, void* dh, void* dA,
+                       void* db, void* dx, void* dz, void* dy, int refine, const void* Q, int64_t sQ, const void* G, int64_t sG,
+                       const void* A, int64_t sA, int32_t* status, const void* lam_lo, const void* slack_lo, qpx_stream_t stream);
+
 /* Batch-MEAN of the gradient of a parameter that the whole batch shares (qp.py:159-177: the reference
  * forms B outer products and then `.mean(0)`): one contraction over the batch instead,
  *   out (r,c) = scale/B * sum_b ( u[b][r] v[b][c] + w[b][r] x[b][c] )        u, w: (B,r)  v, x: (B,c)

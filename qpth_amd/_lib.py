@@ -67,6 +67,11 @@ _SIGNATURES = {
     "qpx_centre_supported": (_i, [_i, _i, _i, _i]),
     "qpx_centre": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                         _vp, _i64, _vp, _i64, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qpx_range_supported": (_i, [_i, _i, _i, _i]),
+    "qpx_ipm_range": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d, _i, _i, _i,
+                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "qpx_backward_range": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "qpx_batch_outer": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, ctypes.c_size_t, _vp]),
     "qpx_batch_outer_workspace_elems": (ctypes.c_size_t, [_i, _i, _i, _i]),
     "qpx_dense_solve": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -227,6 +232,25 @@ class QpxLib:
             _ptr(nu), _ptr(dl_dz), _ptr(dQ), _ptr(dp), _ptr(dG), _ptr(dh), _ptr(dA), _ptr(db),
             _ptr(dx), _ptr(dz), _ptr(dy), int(refine), Qp.ptr, Qp.stride, Gp.ptr, Gp.stride, Ap.ptr, Ap.stride,
             _ptr(status), _stream(factors)))
+
+    # -- two-sided rows lower <= G z <= h: the loop's and the backward's range role, float64
+    def ipm_range(self, B, n, m, q, p, h, lower, gt1, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
+                  zhat, nu, lam, slack, lam_lo, slack_lo, iters, status, best_resid, trace=None):
+        """lower (B,m), (1,m) or (m,) (shared: batch stride 0), -inf = a one-sided row; gt1 (B,) = || G^T e || or None (0)"""
+        pp, hp, bp, lp = Param(p, 2), Param(h, 2), Param(b, 2), Param(lower, 2)
+        self.check(self.dll.qpx_ipm_range(
+            _dtype_code(factors), B, n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
+            _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
+            _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid), _ptr(trace),
+            lp.ptr, lp.stride, _ptr(gt1), _ptr(lam_lo), _ptr(slack_lo), _stream(factors)))
+
+    def backward_range(self, B, n, m, q, factors, sfac, zhat, lam, slack, lam_lo, slack_lo, nu, dl_dz, dQ, dp, dG, dA, db,
+                       status, dx=None, dz=None, dy=None):
+        """Any of dQ..db may be None (gradient not wanted); dz = v, from which the caller forms dh and dlower"""
+        self.check(self.dll.qpx_backward_range(
+            _dtype_code(factors), B, n, m, q, _ptr(factors), int(sfac), _ptr(zhat), _ptr(lam), _ptr(slack), _ptr(nu),
+            _ptr(dl_dz), _ptr(dQ), _ptr(dp), _ptr(dG), None, _ptr(dA), _ptr(db), _ptr(dx), _ptr(dz), _ptr(dy), 0,
+            None, 0, None, 0, None, 0, _ptr(status), _ptr(lam_lo), _ptr(slack_lo), _stream(factors)))
 
     # -- forward mode (QPFunctionFn.jvp): the tangent of the solution, one KKT solve with the backward's matrix
     def jvp(self, B, n, m, q, factors, sfac, zhat, lam, slack, nu, tQ, tp, tG, th, tA, tb, dzhat, status,

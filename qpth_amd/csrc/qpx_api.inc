@@ -414,6 +414,70 @@ inline int api_backward2(KktArgs<double>& a, void* stream)
     return QPX_ERR_UNSUPPORTED;
 }
 
+// Two-sided rows (qpx_ipm_range, qpx_backward_range; DESIGN 4.11): the range role of the loop forms (qpx_forms.h: kIpmRangeRole)
+// and of the backward (kKktRangeRole), float64 arithmetic.  Which form serves a size follows api_ipm's / api_kkt's rule for
+// float64; a form without the role -- the two-wave tile forms and the small thread-grid forms, reachable through the A/B knob
+// alone -- declines, it never falls through to a kernel that reads another image of the blob.  launch = false: the decision only.
+inline int api_ipm_range(IpmArgs<double>& a, void* stream, bool launch)
+{
+    const int n = a.n, m = a.m, q = a.q;
+    if (!use_grid(n, m, q)) return QPX_ERR_UNSUPPORTED;            // the large-QP family has no such role
+    a.images = blob_images<double>(n, m, q);
+    if (a.images == 4) {
+        const int nbt = tile_nb(m);
+        const int nst = slots_for(n, 16 * nbt, q);
+        const int nw = tile_waves(nbt, a.B);
+        const bool ch = tile_chain(nbt, nw);
+        const size_t tb = lds_elems_ipm_tile(nbt, nw, n, q, ch, true) * sizeof(double);
+        if (tb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
+#define QPX_PICK(NBL, NW, NS, CH) \
+        if (nbt == NBL && nw == NW && nst == NS && ch == CH) return launch ? launch_ipm_tile<NBL + kIpmRangeRole, NW, NS, CH>(a, tb, stream) : QPX_OK;
+        QPX_FORMS_IPM_RANGE_TILE(QPX_PICK)
+#undef QPX_PICK
+        return QPX_ERR_UNSUPPORTED;
+    }
+    const int nbg = grid_nb(m);
+    const int nsg = slots_for(n, 16 * nbg, q);
+    const size_t gb = lds_elems_ipm_grid(16, nbg, n, q, true) * sizeof(double);
+    if (gb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
+#define QPX_PICK(NBL, NS) if (nbg == NBL && nsg == NS) return launch ? launch_ipm_grid<double, NBL + kIpmRangeRole, NS>(a, gb, stream) : QPX_OK;
+    QPX_FORMS_IPM_RANGE_GRID(QPX_PICK)
+#undef QPX_PICK
+    return QPX_ERR_UNSUPPORTED;
+}
+inline int api_backward_range(KktArgs<double>& a, void* stream, bool launch)
+{
+    const int n = a.n, m = a.m, q = a.q;
+    if (!use_grid(n, m, q)) return QPX_ERR_UNSUPPORTED;
+    a.images = blob_images<double>(n, m, q);
+    if (a.images == 4) {
+        const int nbt = tile_nb(m);
+        const int nw = tile_waves(nbt, a.B);
+        const bool ch = tile_chain(nbt, nw);
+        const size_t tb = lds_elems_kkt_tile(nbt, nw, n, q, ch) * sizeof(double);
+#define QPX_PICK(NBL, NW, CH) if (nbt == NBL && nw == NW && ch == CH) return launch ? launch_kkt_tile<kKktRangeRole + NBL, NW, true, CH>(a, tb, stream) : QPX_OK;
+        QPX_FORMS_KKT_RANGE_TILE(QPX_PICK)
+#undef QPX_PICK
+        return QPX_ERR_UNSUPPORTED;
+    }
+    const int nbg = grid_nb(m);
+    const size_t gb = lds_elems_kkt_grid(16, nbg, n, q) * sizeof(double);
+#define QPX_PICK(NBL) if (nbg == NBL) return launch ? launch_kkt_grid<double, kKktRangeRole + NBL, true>(a, gb, stream) : QPX_OK;
+    QPX_FORMS_KKT_GRID(QPX_PICK)
+#undef QPX_PICK
+    return QPX_ERR_UNSUPPORTED;
+}
+// (B: the batch the tile forms' waves per QP depend on)
+inline bool range_served(int dtype, int n, int m, int q, int B)
+{
+    if (dtype != QPX_F64) return false;
+    IpmArgs<double> ia{};
+    ia.B = B; ia.n = n; ia.m = m; ia.q = q;
+    KktArgs<double> ka{};
+    ka.B = B; ka.n = n; ka.m = m; ka.q = q;
+    return api_ipm_range(ia, nullptr, false) == QPX_OK && api_backward_range(ka, nullptr, false) == QPX_OK;
+}
+
 // the finishing stage: every family has it (thread-grid / tile kernels: one kernel, the blob's register image of R decides the
 // form; large-QP family: qpx_big_polish.h)
 inline bool polish_served(int dtype, int n, int m, int q)
@@ -795,6 +859,61 @@ int qpx_backward2(int dtype, int B, int n, int m, int q, void* factors, int64_t 
     a.dA = q > 0 ? (double*)HA : nullptr; a.db = q > 0 ? (double*)Hb : nullptr;
     a.status = status;
     return qpx::api_backward2(a, stream);
+}
+
+int qpx_range_supported(int dtype, int n, int m, int q)
+{
+    if (qpx::check_dims(dtype, 1, n, m, q) != QPX_OK) return 0;
+    // (a small and a large batch cover both choices of the tile forms' waves per QP)
+    return qpx::range_served(dtype, n, m, q, 1) && qpx::range_served(dtype, n, m, q, 1 << 20) ? 1 : 0;
+}
+
+int qpx_ipm_range(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
+                  const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
+                  int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
+                  void* best_resid, void* trace, const void* lower, int64_t slo, const void* gt1, void* lam_lo,
+                  void* slack_lo, qpx_stream_t stream)
+{
+    const int e = qpx::check_dims(dtype, B, n, m, q);
+    if (e) return e;
+    if (!p || !h || !lower || !factors || !zhat || !lam || !slack || !lam_lo || !slack_lo || !iters || !status || !best_resid ||
+        (q > 0 && (!nu || !b)))
+        return QPX_ERR_ARG;
+    if (maxIter < 0 || stall_policy < 0 || stall_policy > 2 || slo < 0) return QPX_ERR_ARG;
+    if (!qpx::range_served(dtype, n, m, q, B)) return QPX_ERR_UNSUPPORTED;
+    qpx::IpmArgs<double> a{};
+    a.B = B; a.n = n; a.m = m; a.q = q;
+    a.p = (const double*)p; a.h = (const double*)h; a.b = (const double*)b;
+    a.sp = sp; a.sh = sh; a.sb = sb;
+    a.fac = (double*)factors; a.fac_stride = (size_t)sfac;
+    a.eps = eps; a.maxIter = maxIter; a.notImprovedLim = notImprovedLim; a.stall_policy = stall_policy;
+    a.zhat = (double*)zhat; a.nu = (double*)nu; a.lam = (double*)lam; a.slack = (double*)slack;
+    a.iters = iters; a.status = status; a.best_resid = (double*)best_resid; a.trace = (double*)trace;
+    a.lower = (const double*)lower; a.slo = slo; a.gt1 = (const double*)gt1;
+    a.lam_lo = (double*)lam_lo; a.slack_lo = (double*)slack_lo;
+    return qpx::api_ipm_range(a, stream, true);
+}
+
+int qpx_backward_range(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat, const void* lam,
+                       const void* slack, const void* nu, const void* dl_dz, void* dQ, void* dp, void* dG, void* dh, void* dA,
+                       void* db, void* dx, void* dz, void* dy, int refine, const void* Q, int64_t sQ, const void* G, int64_t sG,
+                       const void* A, int64_t sA, int32_t* status, const void* lam_lo, const void* slack_lo, qpx_stream_t stream)
+{
+    (void)Q; (void)sQ; (void)G; (void)sG; (void)A; (void)sA;        // (qpx_backward's refinement data: refine > 0 is not served)
+    const int e = qpx::check_dims(dtype, B, n, m, q);
+    if (e) return e;
+    if (!factors || !zhat || !lam || !slack || !lam_lo || !slack_lo || !dl_dz || (q > 0 && !nu)) return QPX_ERR_ARG;
+    if (refine < 0) return QPX_ERR_ARG;
+    if (refine > 0 || !qpx::range_served(dtype, n, m, q, B)) return QPX_ERR_UNSUPPORTED;
+    qpx::KktArgs<double> a{};
+    a.B = B; a.n = n; a.m = m; a.q = q; a.fac = (double*)factors; a.fac_stride = (size_t)sfac;
+    a.zhat = (const double*)zhat; a.lam = (const double*)lam; a.slack = (const double*)slack; a.nu = (const double*)nu;
+    a.lam_lo = (const double*)lam_lo; a.slack_lo = (const double*)slack_lo;
+    a.dl_dz = (const double*)dl_dz;
+    a.dQ = (double*)dQ; a.dp = (double*)dp; a.dG = (double*)dG; a.dh = (double*)dh; a.dA = (double*)dA; a.db = (double*)db;
+    a.dx = (double*)dx; a.dz = (double*)dz; a.dy = (double*)dy;
+    a.status = status;
+    return qpx::api_backward_range(a, stream, true);
 }
 
 int qpx_polish_supported(int dtype, int n, int m, int q)

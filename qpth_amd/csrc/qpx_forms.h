@@ -47,6 +47,14 @@ constexpr int kPrefacSoft = 64;
 // finishing forms hold none of its code.
 constexpr int kPolishCentreRole = 64;
 
+// Two-sided rows l <= G z <= h (qpx_ipm_range, qpx_backward_range), float64 arithmetic only.  The loop forms of
+// QPX_FORMS_IPM_RANGE_TILE / _GRID exist a second time as the RANGE role (qpx_grid.h: ipm_loop_role, kRange): blocks / tile
+// rows + kIpmRangeRole in the form's FIRST parameter, as above (ipm_grid_body / ipm_tile_body decode it); the one-sided forms
+// hold none of its code.  The backward of every KKT form the default dispatch picks has a range role too, block / tile rows +
+// kKktRangeRole (kkt_grid_body / kkt_tile_body): d = d_upper + d_lower and lam_upper - lam_lower in the outer products.
+constexpr int kIpmRangeRole = 64;
+constexpr int kKktRangeRole = 256;
+
 }  // namespace qpx
 
 // thread-grid kernels: (blocks of 16 -- of 8 in the one-wave grid -- per side), (blocks, slots of 64 columns)
@@ -66,4 +74,12 @@ constexpr int kPolishCentreRole = 64;
     X(1, 1, false) X(2, 1, false) X(4, 1, false) X(4, 2, false) X(7, 2, false) X(7, 4, true) X(4, 4, true)   // each in the three roles, as above
 #define QPX_FORMS_KKT_B2_TILE(X) X(1, 1, false) X(2, 1, false) X(4, 1, false) X(7, 4, true) X(4, 4, true)            // the second-order role (kKktB2Role)
 #define QPX_FORMS_POLISH_TILE(X) X(1, 1, false) X(2, 1, false) X(4, 1, false) X(4, 4, true) X(7, 4, true)
+// the range role of the loop (kIpmRangeRole): the forms the default dispatch picks, f64 -- (tile rows, waves, slots, chain) / (blocks, slots)
+#define QPX_FORMS_IPM_RANGE_TILE(X)                                                                              \
+    X(1, 1, 1, false) X(1, 1, 2, false) X(1, 1, 4, false) X(2, 1, 1, false) X(2, 1, 2, false) X(2, 1, 4, false)  \
+    X(4, 1, 1, false) X(4, 1, 2, false) X(4, 1, 4, false)                                                        \
+    X(7, 4, 2, true) X(7, 4, 4, true) X(4, 4, 1, true) X(4, 4, 2, true) X(4, 4, 4, true)
+#define QPX_FORMS_IPM_RANGE_GRID(X) X(10, 4) X(13, 4)
+// ... and of the backward (kKktRangeRole): the tile forms of the second-order role (the default dispatch's), every thread-grid form
+#define QPX_FORMS_KKT_RANGE_TILE(X) QPX_FORMS_KKT_B2_TILE(X)
 #define QPX_FORMS_PREFAC_TILE(X) X(4, false) X(7, false) X(4, true) X(7, true)    // (tile rows of nz + neq, with equalities)

@@ -274,16 +274,17 @@ template <class T, int GS, int NBL> struct GridMat {
 
 // LDS elements of the loop kernel: 17 vectors of v = 64 NS >= max(n, MP, q), 16 scalars + 8 control
 // words, scratch
-QPX_LAYOUT_HD size_t lds_elems_ipm_loop(size_t mp, size_t scratch, int n, int q)
+// (range role: ten more vectors, the lower side's -- ipm_loop_role)
+QPX_LAYOUT_HD size_t lds_elems_ipm_loop(size_t mp, size_t scratch, int n, int q, bool range = false)
 {
     const size_t d = max2(max2((size_t)n, mp), (size_t)q);
     const size_t v = d <= 64 ? 64 : (d <= 128 ? 128 : (d <= 256 ? 256 : 512));    // 64 NS, see ipm_loop_body
-    return 17 * v + 24 + scratch;
+    return (range ? 27 : 17) * v + 24 + scratch;
 }
-QPX_LAYOUT_HD size_t lds_elems_ipm_grid(int gs, int nbl, int n, int q)
+QPX_LAYOUT_HD size_t lds_elems_ipm_grid(int gs, int nbl, int n, int q, bool range = false)
 {
     const size_t mg = (size_t)gs * nbl;
-    return lds_elems_ipm_loop(mg, 2 * mg + 4 + (size_t)nbl * gs * gs, n, q);
+    return lds_elems_ipm_loop(mg, 2 * mg + 4 + (size_t)nbl * gs * gs, n, q, range);
 }
 
 // out[c] (op)= sum_r Mat[r][c] * vec[r]   -- thread per column c: the loads of a row are
@@ -905,9 +906,222 @@ QPX_DEV void ipm_final_step(const Block& b, int lane, int m, T* vZ, T* vS, const
 }
 
 // ------------------------------------------------------------------------------------------
+// The same blocks for TWO-SIDED rows l <= g_i'z <= u_i (the loop's range role).  The reference's QP has the rows
+// [G; -G_F] z <= [u; -l_F] (F: the rows with a finite l); its Newton system collapses to the m x m system of the one-sided
+// loop with the diagonal 1/(wu + wl), wu = zu/su, wl = zl/sl (0 off F):
+//   (R + diag(1/(wu+wl))) v = -(wu qu - wl ql)/(wu+wl),   R v = -rhs - v/(wu+wl),   dzu = wu (-qu - R v),   dzl = wl (-ql + R v).
+// The lower side's z, s, 1/z, 1/s, directions and best iterate are LDS vectors beside the upper side's; vH = u - l marks the
+// rows: finite on F, +inf on a one-sided row, which runs the one-sided row's very operations (zl = 0, sl = +inf are only ever
+// written out).  1/z, 1/s of both sides and vD = 1/(wu+wl) (s/z on a one-sided row) are formed where z and s are -- at the
+// end of the start point and of the combined step -- so that the diagonal is final when a pass begins (the tile waves of
+// the chain-wave form read it there) and the blocks on the chain multiply by reciprocals already held.
+template <class T> QPX_DEV bool two_sided_(T hl) { return hl < Lim<T>::inf(); }
+// the reciprocals and the diagonal of the iterate (zu, su, zl, sl) of row i
+template <class T> QPX_DEV void range_recips(bool f, int i, T zu, T su, T zl, T sl, T* vRZ, T* vRS, T* vRZL, T* vRSL, T* vD)
+{
+    const T rzu = rcp_(zu), rsu = rcp_(su);
+    vRZ[i] = rzu;
+    vRS[i] = rsu;
+    if (f) {
+        const T rzl = rcp_(zl), rsl = rcp_(sl);
+        vRZL[i] = rzl;
+        vRSL[i] = rsl;
+        vD[i] = rcp_(zu * rsu + zl * rsl);
+    } else {
+        vD[i] = su * rzu;
+    }
+}
+// Start point: w = 1 on the live entries, vX = v = -T^-1 (cu - f cl)/(1 + f), T = R + diag(1/(1 + f)); xu = -cu - R v,
+// xl = -cl + R v are the reference's z_i = -s_i of the doubled QP, shifted as there by the minima over all live entries
+template <class T, int NS>
+QPX_DEV void range_start_point(const Block& b, int lane, int m, int M8, const T* vX, const T* vRH, const T* vC, const T* vH, T* vZ, T* vS,
+                               T* vZL, T* vSL, T* vRZ, T* vRS, T* vRZL, T* vRSL, T* vD, T* vA, T* vBZ, T* vBS, T* vBZL, T* vBSL,
+                               T* pSigz, T* pSigs)
+{
+    T xu[NS], xl[NS];
+    T mnz = Lim<T>::inf(), mns = Lim<T>::inf();
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        xu[k] = T(0); xl[k] = T(0);
+        if (i < m) {
+            const T hl = vH[i], x = vX[i];
+            if (two_sided_(hl)) {
+                const T c = vC[i], rv = -vRH[i] - x * vD[i];
+                xu[k] = -c - rv;
+                xl[k] = rv - (hl - c);
+                mnz = min2_(mnz, xl[k]);
+                mns = min2_(mns, -xl[k]);
+            } else {
+                xu[k] = x;
+            }
+            mnz = min2_(mnz, xu[k]);
+            mns = min2_(mns, -xu[k]);
+        }
+    }
+    mnz = wave_min(b, mnz);
+    mns = wave_min(b, mns);
+    const T sigz = (mnz < T(0)) ? (T(1) - mnz) : T(0);
+    const T sigs = (mns < T(0)) ? (T(1) - mns) : T(0);
+    if (lane == 0) { *pSigz = sigz; *pSigs = sigs; }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const bool f = two_sided_(vH[i]);
+            const T zu = xu[k] + sigz, su = -xu[k] + sigs;
+            const T zl = f ? xl[k] + sigz : T(0), sl = f ? -xl[k] + sigs : Lim<T>::inf();
+            vZ[i] = zu; vS[i] = su; vZL[i] = zl; vSL[i] = sl;
+            vBZ[i] = zu; vBS[i] = su; vBZL[i] = zl; vBSL[i] = sl;
+            vA[i] = xu[k] - xl[k];
+            range_recips(f, i, zu, su, zl, sl, vRZ, vRS, vRZL, vRSL, vD);
+        } else if (i < M8) {
+            vA[i] = T(0);
+        }
+    }
+}
+// Affine step lengths, centring sigma, the corrector's right-hand side.  vX = v of the affine solve, vRH its right-hand side
+// (overwritten by the corrector's), vQU = qu = cu + R y of this pass (overwritten by the lower side's corrector rs: one vector)
+template <class T, int NS>
+QPX_DEV void range_affine_step(const Block& b, int lane, int m, T mu, T szdot, const T* vH, const T* vZ, const T* vS, const T* vZL,
+                               const T* vSL, const T* vRZ, const T* vRS, const T* vRZL, const T* vRSL, const T* vD, const T* vX,
+                               T* vRH, T* vQUL, T* vRSC, T* vDZA, T* vDSA, T* vDZAL, T* vDSAL)
+{
+    T dzu[NS], dsu[NS], dzl[NS], dsl[NS];
+    T t = T(0);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        dzu[k] = T(0); dsu[k] = T(0); dzl[k] = T(0); dsl[k] = T(0);
+        if (i < m) {
+            const T hl = vH[i], x = vX[i], su = vS[i];
+            if (two_sided_(hl)) {
+                // qu + R v, then the side with the SMALLER w by its formula and the other from v = dzu - dzl: w (-q -+ R v) on the
+                // larger side is a small difference of O(1) numbers times w ~ 1/mu
+                const T tq = vQUL[i] + (-vRH[i] - x * vD[i]);
+                const T sl = vSL[i], wu = vZ[i] * vRS[i], wl = vZL[i] * vRSL[i];
+                if (wu >= wl) {
+                    dzl[k] = wl * (tq - hl);
+                    dzu[k] = x + dzl[k];
+                } else {
+                    dzu[k] = -wu * tq;
+                    dzl[k] = dzu[k] - x;
+                }
+                dsu[k] = -su - dzu[k] * (su * vRZ[i]);
+                dsl[k] = -sl - dzl[k] * (sl * vRZL[i]);
+            } else {
+                dzu[k] = x;
+                dsu[k] = -su - x * vD[i];
+            }
+            if (dzu[k] < T(0)) t = max2_(t, -dzu[k] * vRZ[i]);
+            if (dsu[k] < T(0)) t = max2_(t, -dsu[k] * vRS[i]);
+            if (dzl[k] < T(0)) t = max2_(t, -dzl[k] * vRZL[i]);
+            if (dsl[k] < T(0)) t = max2_(t, -dsl[k] * vRSL[i]);
+        }
+    }
+    t = wave_max(b, t);
+    T al = (t > T(0)) ? T(1) / t : T(1);
+    al = (al < T(1)) ? al : T(1);
+    T t3 = 0;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            t3 = fma_(vS[i] + al * dsu[k], vZ[i] + al * dzu[k], t3);
+            if (two_sided_(vH[i])) t3 = fma_(vSL[i] + al * dsl[k], vZL[i] + al * dzl[k], t3);
+        }
+    }
+    t3 = wave_sum(b, t3);
+    T sig = t3 / szdot;
+    sig = sig * sig * sig;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const bool f = two_sided_(vH[i]);
+            const T rsu = (-mu * sig + dsu[k] * dzu[k]) * vRS[i];
+            const T rsl = f ? (-mu * sig + dsl[k] * dzl[k]) * vRSL[i] : T(0);
+            vRSC[i] = rsu;
+            vQUL[i] = rsl;
+            vRH[i] = (rsu - rsl) * vD[i];
+            vDZA[i] = dzu[k]; vDSA[i] = dsu[k];
+            vDZAL[i] = dzl[k]; vDSAL[i] = dsl[k];
+        }
+    }
+}
+// The combined step with the 0.999 damping, tau, z' = (zu - zl) - tau sigma_z e, and the next pass's reciprocals and diagonal
+template <class T, int NS>
+QPX_DEV void range_final_step(const Block& b, int lane, int m, const T* vH, T* vZ, T* vS, T* vZL, T* vSL, T* vRZ, T* vRS, T* vRZL,
+                              T* vRSL, T* vD, const T* vX, const T* vRH, const T* vRSC, const T* vRSCL, const T* vDZA, const T* vDSA,
+                              const T* vDZAL, const T* vDSAL, T* vA, T* pTau, T* pAlphaPrev, T sigz)
+{
+    T dzu[NS], dsu[NS], dzl[NS], dsl[NS];
+    T t = T(0);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        dzu[k] = T(0); dsu[k] = T(0); dzl[k] = T(0); dsl[k] = T(0);
+        if (i < m) {
+            const T x = vX[i];
+            if (two_sided_(vH[i])) {
+                const T rv = -vRH[i] - x * vD[i];
+                const T su = vS[i], sl = vSL[i], wu = vZ[i] * vRS[i], wl = vZL[i] * vRSL[i];
+                const T rsu = vRSC[i], rsl = vRSCL[i];
+                T cu, cl;                    // the corrector's dz: the smaller w's side by its formula, as in the affine step
+                if (wu >= wl) {
+                    cl = wl * rv - rsl;
+                    cu = x + cl;
+                } else {
+                    cu = -rsu - wu * rv;
+                    cl = cu - x;
+                }
+                dzu[k] = vDZA[i] + cu;
+                dzl[k] = vDZAL[i] + cl;
+                dsu[k] = vDSA[i] + (-rsu - cu) * (su * vRZ[i]);
+                dsl[k] = vDSAL[i] + (-rsl - cl) * (sl * vRZL[i]);
+            } else {
+                dzu[k] = vDZA[i] + x;
+                dsu[k] = vDSA[i] + (-vRSC[i] - x) * vD[i];
+            }
+            if (dzu[k] < T(0)) t = max2_(t, -dzu[k] * vRZ[i]);
+            if (dsu[k] < T(0)) t = max2_(t, -dsu[k] * vRS[i]);
+            if (dzl[k] < T(0)) t = max2_(t, -dzl[k] * vRZL[i]);
+            if (dsl[k] < T(0)) t = max2_(t, -dsl[k] * vRSL[i]);
+        }
+    }
+    t = wave_max(b, t);
+    T al = (t > T(0)) ? T(1) / t : T(1);
+    al = T(0.999) * al;
+    al = (al < T(1)) ? al : T(1);
+    const T tau = (T(1) - al) * *pTau;
+    const T tsz = tau * sigz;
+    b.wave_sync();           // every lane has read the old tau
+    if (lane == 0) { *pTau = tau; *pAlphaPrev = al; }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const bool f = two_sided_(vH[i]);
+            const T zu = fma_(al, dzu[k], vZ[i]), su = fma_(al, dsu[k], vS[i]);
+            vZ[i] = zu; vS[i] = su;
+            T zl = T(0), sl = Lim<T>::inf();
+            if (f) {
+                zl = fma_(al, dzl[k], vZL[i]);
+                sl = fma_(al, dsl[k], vSL[i]);
+                vZL[i] = zl; vSL[i] = sl;
+            }
+            vA[i] = f ? (zu - zl) : (zu - tsz);
+            range_recips(f, i, zu, su, zl, sl, vRZ, vRS, vRZL, vRSL, vD);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // The PDIPM loop on the format-3 blob.  Mathematics and control flow: see ipm_body (same
 // reference citations); the factorisation is ldl_inv and every solve is two triangular mat-vecs.
-template <class T, class Mat, int NS, class P>
+// kRange: the form's range role (qpx_forms.h: kIpmRangeRole) -- two-sided rows, the range_* blocks above; the one-sided forms
+// compile none of it.
+template <class T, class Mat, int NS, bool kRange, class P>
 QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, const P& g)
 {
     constexpr int M8 = Mat::MP, NT = Mat::NT;
@@ -941,33 +1155,58 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     T* vDSA = vRS + v;    // ... and the corrector right-hand side rs
     T* vRSC = vDSA + v;
     T* vX0 = vRSC + v;    // x0 = -K p (n): formed with c at the start, while p's products share their loads' flight
-    T* sc = vX0 + v;                                // 16 scalars of the IPM state
+    // range role: the lower side's z, s, their reciprocals, best iterate and affine step; vQUL is qu = cu + R y from the
+    // right-hand side block to the affine step and the lower side's corrector rs from there on; vH = u - l (+inf: one-sided)
+    T* vZL = vX0 + v;
+    T* vSL = vZL + v;
+    T* vRZL = vSL + v;
+    T* vRSL = vRZL + v;
+    T* vBZL = vRSL + v;
+    T* vBSL = vBZL + v;
+    T* vDZAL = vBSL + v;
+    T* vDSAL = vDZAL + v;
+    T* vQUL = vDSAL + v;
+    T* vH = vQUL + v;
+    T* sc = kRange ? vH + v : vX0 + v;              // 16 scalars of the IPM state
     int* ctrl = reinterpret_cast<int*>(sc + 16);    // 8 elements of control words
     T* scr = sc + 24;     // Mat::scratch_elems()
 
     const int lane = b.lane();
     const bool w0 = g.lead(b);        // the wave that does the O(m) vector work
-    const T mT = (T)m;
+    T mT = (T)m;          // (range role: m', the live rows of the doubled QP, from behind the prologue on)
     const int io32 = a.io32;
     const In<T> pg(a.p, (size_t)qp * a.sp, io32), hg(a.h, (size_t)qp * a.sh, io32);
     const In<T> bg(q > 0 ? a.b : nullptr, (size_t)qp * a.sb, io32);
+    const In<T> lwg(kRange ? a.lower : nullptr, (size_t)qp * a.slo, io32);
 
-    if (a.status[qp] & (QPX_ST_Q_NOT_SPD | QPX_ST_A_RANK)) {
+    // range role: a lower bound that is NaN, +inf or not below its h -- every wave looks at all of them, so the decision is uniform
+    bool bad_lower = false;
+    if constexpr (kRange) {
+        for (int i = b.lane(); i < m; i += kWave)
+            if (!(lwg[i] < hg[i])) bad_lower = true;
+        bad_lower = b.any(bad_lower);
+    }
+    if ((a.status[qp] & (QPX_ST_Q_NOT_SPD | QPX_ST_A_RANK)) || bad_lower) {
         const T nanv = Lim<T>::inf() - Lim<T>::inf();
         for (int i = b.tid; i < n; i += b.nt) put_(a.zhat, io32, (size_t)qp * n + i, nanv);
         for (int i = b.tid; i < m; i += b.nt) {
             put_(a.lam, io32, (size_t)qp * m + i, nanv);
             put_(a.slack, io32, (size_t)qp * m + i, nanv);
+            if constexpr (kRange) {
+                put_(a.lam_lo, io32, (size_t)qp * m + i, nanv);
+                put_(a.slack_lo, io32, (size_t)qp * m + i, nanv);
+            }
         }
         for (int i = b.tid; i < q; i += b.nt) put_(a.nu, io32, (size_t)qp * q + i, nanv);
         if (b.tid == 0) {
             a.iters[qp] = 0;
             put_(a.best_resid, io32, (size_t)qp, Lim<T>::inf());
             if (a.warm_used) a.warm_used[qp] = 0;
+            if (bad_lower) a.status[qp] |= QPX_ST_NONFINITE;
         }
         return;
     }
-    enum { kTau = 0, kBtau, kSigz, kSigs, kBres, kFeasPrev, kAlphaPrev, kMu, kSzdot, kFeas, kResid, kGt1 };
+    enum { kTau = 0, kBtau, kSigz, kSigs, kBres, kFeasPrev, kAlphaPrev, kMu, kSzdot, kFeas, kResid, kGt1, kMp };
     enum { kStop = 0, kNnot, kFloor, kSt, kIters, kWarm };
     QPX_PROF_INIT
     // ---- c = h - G x0 = h + M p - W b   (x0 = -K p + N b is formed only at the end)
@@ -1010,12 +1249,42 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     if (b.tid == 0) {
         sc[kTau] = T(1); sc[kBtau] = T(1); sc[kSigz] = T(0); sc[kSigs] = T(0); sc[kBres] = Lim<T>::inf();
         sc[kFeasPrev] = T(0); sc[kAlphaPrev] = T(0);
-        sc[kGt1] = F[lay.scal];          // || G^T 1 ||: read from the blob once, not once per iteration (a global load on the chain)
+        // || G^T 1 ||: read from the blob once, not once per iteration (a global load on the chain).  Range role: || G^T e ||,
+        // e = 1 on the one-sided rows, from the caller -- the blob's scalar is that number only when no row is two-sided
+        if constexpr (kRange) sc[kGt1] = a.gt1 ? In<T>(a.gt1, (size_t)qp, io32)[0] : T(0);
+        else sc[kGt1] = F[lay.scal];
         ctrl[kStop] = 0; ctrl[kNnot] = 0; ctrl[kFloor] = 0; ctrl[kSt] = 0; ctrl[kIters] = 0;
     }
     for (int i = b.tid; i < M8; i += NT) {
         vZ[i] = T(1); vS[i] = T(1); vRZ[i] = T(1); vRS[i] = T(1);
         vDSA[i] = T(0); vRSC[i] = T(0);
+        if constexpr (kRange) {
+            // the start point's system (c is final behind the barrier above): T = R + diag(1/(1 + f)), right-hand side
+            // (cu - f cl)/(1 + f) in vRH (= vB: first written by the mat-vec of pass 0), and e in vA for R e
+            // (a row is two-sided where u - l is finite -- two_sided_, the one test every block uses; -inf gives +inf)
+            T hl = Lim<T>::inf(), rh = T(0), dd = T(1), e = T(1);
+            if (i < m) {
+                const T c = vC[i];
+                hl = hg[i] - lwg[i];
+                rh = c;
+                if (two_sided_(hl)) {
+                    rh = T(0.5) * (c - (hl - c));
+                    dd = T(0.5);
+                    e = T(0);
+                }
+            }
+            vH[i] = hl; vRH[i] = rh; vD[i] = dd; vA[i] = e;
+            vZL[i] = T(1); vSL[i] = T(1); vRZL[i] = T(1); vRSL[i] = T(1);
+            vDZAL[i] = T(0); vDSAL[i] = T(0); vQUL[i] = T(0);
+        }
+    }
+    if constexpr (kRange) {
+        if (w0) {            // m' = m + the two-sided rows: the live rows of the doubled QP
+            T cnt = T(0);
+            for (int i = lane; i < m; i += kWave) cnt += two_sided_(hg[i] - lwg[i]) ? T(1) : T(0);
+            cnt = wave_sum(b, cnt);
+            if (lane == 0) sc[kMp] = mT + cnt;
+        }
     }
     // ---- the warm entry: z = max(lam0, f), s = max(s0, f), z' = z (sigma_z = sigma_s = 0, tau = 1 as set above): x = x0 - M^T z
     // and nu = nu0 - W^T z are dual- and equality-feasible by construction, so pass -1 (the start point: one factorisation and
@@ -1039,6 +1308,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     if (b.tid == 0 && a.warm_used) a.warm_used[qp] = warm;
     const int it0 = warm ? 0 : -1;
     Mat::sync(b);
+    if constexpr (kRange) mT = sc[kMp];
 
     // ---- pass -1 is the start point: T = R + I, z_i = -T^-1 c, s_i = -z_i, shifts (batch.py:61-87),
     // and R 1 on the way; passes 0.. are the IPM iterations.  One loop so that the factorisation and
@@ -1070,10 +1340,14 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                     if (i < m) {
                         const T zk = vZ[i], sk = vS[i];
                         szdot = fma_(sk, zk, szdot);
-                        const T rzk = rcp_(zk);
-                        vRZ[i] = rzk;
-                        vRS[i] = rcp_(sk);
-                        vD[i] = sk * rzk;
+                        if constexpr (kRange) {      // (the reciprocals and the diagonal were formed with the iterate: range_recips)
+                            if (two_sided_(vH[i])) szdot = fma_(vSL[i], vZL[i], szdot);
+                        } else {
+                            const T rzk = rcp_(zk);
+                            vRZ[i] = rzk;
+                            vRS[i] = rcp_(sk);
+                            vD[i] = sk * rzk;
+                        }
                     }
                 }
                 szdot = wave_sum(b, szdot);
@@ -1083,7 +1357,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             Mat::ahead_pivot0(b, g, ah, vD, scr, rd, m);
         }
         QPX_PROF(4)
-        Mat::ahead_front(b, g, E, vA, vZ, vS, scr);      // tile waves: partial sums of R z' (first pass: R 1), T = R + diag(s/z), panel 0's old rows
+        Mat::template ahead_front<kRange>(b, g, E, vA, vZ, kRange ? vD : vS, scr);      // tile waves: partial sums of R z' (first pass: R 1), T = R + diag(s/z), panel 0's old rows
         Mat::sync(b);
         QPX_PROF(3)                  // (profiling build, chain wave: its wait for the tile waves)
         const int rc = Mat::ldl_inv_ahead(b, g, E, scr, rd, m, [&] { Mat::ahead_gather(b, lane, scr, first ? vR1 : vB); }, [&] {
@@ -1096,6 +1370,13 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 if (i < m) {
                     const T rz = vS[i] - vC[i] - vB[i];
                     pri2 = fma_(rz, rz, pri2);
+                    if constexpr (kRange) {
+                        const T hl = vH[i];
+                        if (two_sided_(hl)) {
+                            const T rl = vSL[i] - (hl - vC[i]) + vB[i];
+                            pri2 = fma_(rl, rl, pri2);
+                        }
+                    }
                 }
             }
             pri2 = wave_sum(b, pri2);
@@ -1111,7 +1392,10 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             const bool better = (it == 0) || (resid < bres);
             if (better) {
                 bres = resid; nnot = 0;
-                for (int i = lane; i < m; i += kWave) { vBZ[i] = vZ[i]; vBS[i] = vS[i]; }
+                for (int i = lane; i < m; i += kWave) {
+                    vBZ[i] = vZ[i]; vBS[i] = vS[i];
+                    if constexpr (kRange) { vBZL[i] = vZL[i]; vBSL[i] = vSL[i]; }
+                }
             } else if (a.stall_policy == 1 || (a.stall_policy == 2 && mT * mu < feas)) {
                 nnot += 1;
             } else {
@@ -1141,7 +1425,17 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
                 const int i = k * kWave + lane;
-                if (i < m) vRH[i] = vC[i] + vB[i] + tsz * vR1[i];       // affine right-hand side c + R z
+                if (i < m) {
+                    const T qu = vC[i] + vB[i] + tsz * vR1[i];          // affine right-hand side c + R z
+                    if constexpr (kRange) {
+                        // qu = cu + R y, ql = cl - R y = (u - l) - qu: (wu qu - wl ql)/(wu + wl); a one-sided row keeps qu
+                        const T hl = vH[i];
+                        vQUL[i] = qu;
+                        vRH[i] = two_sided_(hl) ? ((vZ[i] * vRS[i]) * qu - (vZL[i] * vRSL[i]) * (hl - qu)) * vD[i] : qu;
+                    } else {
+                        vRH[i] = qu;
+                    }
+                }
             }
         }, [&] { return first ? 0 : ctrl[kStop]; });
         QPX_PROF(5)
@@ -1152,6 +1446,9 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 if (first) {
                     for (int i = lane; i < M8; i += kWave) {
                         if (i < m) { vBZ[i] = T(1); vBS[i] = T(1); }
+                        if constexpr (kRange) {
+                            if (i < m) { const bool f = two_sided_(vH[i]); vBZL[i] = f ? T(1) : T(0); vBSL[i] = f ? T(1) : Lim<T>::inf(); }
+                        }
                         vA[i] = T(0);
                     }
                 }
@@ -1159,15 +1456,23 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             break;
         }
         QPX_PROF(1)
-        Mat::template solve_neg<true>(b, g, E, rd, m, first ? vC : vRH, vX, vTm, scr);
+        Mat::template solve_neg<true>(b, g, E, rd, m, (first && !kRange) ? vC : vRH, vX, vTm, scr);
         QPX_PROF(6)
         if (first) {
-            if (w0) ipm_start_point<T, NS>(b, lane, m, M8, vX, vZ, vS, vA, vBZ, vBS, sc + kSigz, sc + kSigs);
+            if (w0) {
+                if constexpr (kRange) range_start_point<T, NS>(b, lane, m, M8, vX, vRH, vC, vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vA,
+                                                               vBZ, vBS, vBZL, vBSL, sc + kSigz, sc + kSigs);
+                else ipm_start_point<T, NS>(b, lane, m, M8, vX, vZ, vS, vA, vBZ, vBS, sc + kSigz, sc + kSigs);
+            }
             Mat::sync(b);
             QPX_PROF(1)
             continue;
         }
-        if (w0) ipm_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vZ, vS, vRZ, vRS, vD, vX, vRSC, vRH, vDZA, vDSA);
+        if (w0) {
+            if constexpr (kRange) range_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vX,
+                                                           vRH, vQUL, vRSC, vDZA, vDSA, vDZAL, vDSAL);
+            else ipm_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vZ, vS, vRZ, vRS, vD, vX, vRSC, vRH, vDZA, vDSA);
+        }
         Mat::sync(b);
         QPX_PROF(1)
         Mat::template solve_neg<true>(b, g, E, rd, m, vRH, vX, vTm, scr);
@@ -1176,7 +1481,11 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         // read them -- so that it arrives under the chain wave's step-length block: measured again in round 6 with the chain
         // wave ahead, 0.4448 against 0.4428 ms, no gain -- profiles/r06g_ab_early_load_two_accumulators.txt; rounds 2 and 3
         // had measured the same with their orders of a pass.)
-        if (w0) ipm_final_step<T, NS>(b, lane, m, vZ, vS, vRZ, vRS, vD, vX, vRSC, vDZA, vDSA, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
+        if (w0) {
+            if constexpr (kRange) range_final_step<T, NS>(b, lane, m, vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vX, vRH, vRSC, vQUL, vDZA,
+                                                          vDSA, vDZAL, vDSAL, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
+            else ipm_final_step<T, NS>(b, lane, m, vZ, vS, vRZ, vRS, vD, vX, vRSC, vDZA, vDSA, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
+        }
         Mat::sync(b);
         QPX_PROF(1)
     }
@@ -1198,12 +1507,29 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                     const T rz = sk - vC[i] - vB[i];
                     pri2 = fma_(rz, rz, pri2);
                     szdot = fma_(sk, zk, szdot);
-                    vRH[i] = vC[i] + vB[i] + tsz * vR1[i];       // affine right-hand side c + R z
-                    // 1/z, 1/s and d = s/z once per iteration: every later division by z or s is a multiplication
-                    const T rzk = rcp_(zk);
-                    vRZ[i] = rzk;
-                    vRS[i] = rcp_(sk);
-                    vD[i] = sk * rzk;
+                    const T qu = vC[i] + vB[i] + tsz * vR1[i];          // affine right-hand side c + R z
+                    if constexpr (kRange) {
+                        // (as the chain-wave order above: the lower side's residual, and the right-hand side of the m x m system;
+                        // the reciprocals and the diagonal were formed with the iterate: range_recips)
+                        const T hl = vH[i];
+                        vQUL[i] = qu;
+                        if (two_sided_(hl)) {
+                            const T zl = vZL[i], sl = vSL[i];
+                            const T rl = sl - (hl - vC[i]) + vB[i];
+                            pri2 = fma_(rl, rl, pri2);
+                            szdot = fma_(sl, zl, szdot);
+                            vRH[i] = ((zk * vRS[i]) * qu - (zl * vRSL[i]) * (hl - qu)) * vD[i];
+                        } else {
+                            vRH[i] = qu;
+                        }
+                    } else {
+                        vRH[i] = qu;
+                        // 1/z, 1/s and d = s/z once per iteration: every later division by z or s is a multiplication
+                        const T rzk = rcp_(zk);
+                        vRZ[i] = rzk;
+                        vRS[i] = rcp_(sk);
+                        vD[i] = sk * rzk;
+                    }
                 }
             }
             pri2 = wave_sum(b, pri2);
@@ -1221,7 +1547,10 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             const bool better = (it == 0) || (resid < bres);
             if (better) {
                 bres = resid; nnot = 0;
-                for (int i = lane; i < m; i += kWave) { vBZ[i] = vZ[i]; vBS[i] = vS[i]; }
+                for (int i = lane; i < m; i += kWave) {
+                    vBZ[i] = vZ[i]; vBS[i] = vS[i];
+                    if constexpr (kRange) { vBZL[i] = vZL[i]; vBSL[i] = vSL[i]; }
+                }
             } else if (a.stall_policy == 1 || (a.stall_policy == 2 && mT * mu < feas)) {
                 nnot += 1;
             } else {
@@ -1260,6 +1589,9 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 if (first) {
                     for (int i = lane; i < M8; i += kWave) {
                         if (i < m) { vBZ[i] = T(1); vBS[i] = T(1); }
+                        if constexpr (kRange) {
+                            if (i < m) { const bool f = two_sided_(vH[i]); vBZL[i] = f ? T(1) : T(0); vBSL[i] = f ? T(1) : Lim<T>::inf(); }
+                        }
                         vA[i] = T(0);
                     }
                 }
@@ -1268,20 +1600,32 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         }
         // first pass: z_i = -T^-1 c; iterations: affine scaling direction dz_aff = -T^-1 (c + R z)
         QPX_PROF(1)
-        Mat::template solve_neg<true>(b, g, E, rd, m, first ? vC : vRH, vX, vTm, scr);
+        Mat::template solve_neg<true>(b, g, E, rd, m, (first && !kRange) ? vC : vRH, vX, vTm, scr);
         QPX_PROF(6)
         if (first) {
-            if (w0) ipm_start_point<T, NS>(b, lane, m, M8, vX, vZ, vS, vA, vBZ, vBS, sc + kSigz, sc + kSigs);
+            if (w0) {
+                if constexpr (kRange) range_start_point<T, NS>(b, lane, m, M8, vX, vRH, vC, vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vA,
+                                                               vBZ, vBS, vBZL, vBSL, sc + kSigz, sc + kSigs);
+                else ipm_start_point<T, NS>(b, lane, m, M8, vX, vZ, vS, vA, vBZ, vBS, sc + kSigz, sc + kSigs);
+            }
             Mat::sync(b);
             QPX_PROF(1)
             continue;
         }
-        if (w0) ipm_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vZ, vS, vRZ, vRS, vD, vX, vRSC, vRH, vDZA, vDSA);
+        if (w0) {
+            if constexpr (kRange) range_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vX,
+                                                           vRH, vQUL, vRSC, vDZA, vDSA, vDZAL, vDSAL);
+            else ipm_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vZ, vS, vRZ, vRS, vD, vX, vRSC, vRH, vDZA, vDSA);
+        }
         Mat::sync(b);
         QPX_PROF(1)
         Mat::template solve_neg<true>(b, g, E, rd, m, vRH, vX, vTm, scr);
         QPX_PROF(6)
-        if (w0) ipm_final_step<T, NS>(b, lane, m, vZ, vS, vRZ, vRS, vD, vX, vRSC, vDZA, vDSA, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
+        if (w0) {
+            if constexpr (kRange) range_final_step<T, NS>(b, lane, m, vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vX, vRH, vRSC, vQUL, vDZA,
+                                                          vDSA, vDZAL, vDSAL, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
+            else ipm_final_step<T, NS>(b, lane, m, vZ, vS, vRZ, vRS, vD, vX, vRSC, vDZA, vDSA, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
+        }
         Mat::sync(b);
         QPX_PROF(1)
     }
@@ -1299,7 +1643,14 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             const T bz = vBZ[i];
             put_(a.lam, io32, (size_t)qp * m + i, bz);
             put_(a.slack, io32, (size_t)qp * m + i, vBS[i]);
-            vA[i] = bz - bts;
+            if constexpr (kRange) {
+                const T bzl = vBZL[i];
+                put_(a.lam_lo, io32, (size_t)qp * m + i, bzl);
+                put_(a.slack_lo, io32, (size_t)qp * m + i, vBSL[i]);
+                vA[i] = two_sided_(vH[i]) ? bz - bzl : bz - bts;
+            } else {
+                vA[i] = bz - bts;
+            }
         }
         if (lane == 0) {
             a.iters[qp] = iters;
@@ -1337,18 +1688,20 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
 }
 
 // The loop body runs once per wave role (the tile kernels' chain-wave form: Mat::with_role); every other form has one.
-template <class T, class Mat, int NS>
+template <class T, class Mat, int NS, bool kRange = false>
 QPX_DEV void ipm_loop_body(const Block& b, const IpmArgs<T>& a, int qp, T* lds)
 {
     typename Mat::Pos g(b);
     g.assign(b, reinterpret_cast<int*>(lds));      // (an LDS word nothing else uses before the barriers inside)
-    Mat::with_role(g, [&](const auto& gp) { ipm_loop_role<T, Mat, NS>(b, a, qp, lds, gp); });
+    Mat::with_role(g, [&](const auto& gp) { ipm_loop_role<T, Mat, NS, kRange>(b, a, qp, lds, gp); });
 }
 
+// (NBL >= kIpmRangeRole: the range role of the form with NBL - kIpmRangeRole blocks, qpx_forms.h)
 template <class T, int GS, int NBL, int NS>
 QPX_DEV void ipm_grid_body(const Block& b, const IpmArgs<T>& a, int qp, T* lds)
 {
-    ipm_loop_body<T, GridMat<T, GS, NBL>, NS>(b, a, qp, lds);
+    if constexpr (NBL >= kIpmRangeRole) ipm_loop_body<T, GridMat<T, GS, NBL - kIpmRangeRole>, NS, true>(b, a, qp, lds);
+    else ipm_loop_body<T, GridMat<T, GS, NBL>, NS>(b, a, qp, lds);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1480,9 +1833,12 @@ QPX_DEV bool kkt_factor(const Block& b, const P& g, typename Mat::Regs& E, const
 // format-3 blob (see kkt_body for the reference citations):
 //   dz = -T^-1 (M rx + W ry + rs/d - rz),  dx = -K rx - M^T dz - N ry,
 //   dy = S11^-1 ry - N^T rx - W^T dz,      ds = (-rs - dz)/d
-template <class T, class Mat, bool kBackward, class P>
+// kRange (the backward only; qpx_forms.h: kKktRangeRole): two-sided rows -- d = d_upper + d_lower from both sides' multipliers
+// and slacks, lam - lam_lo where lam meets dx in dG; dz is v of DESIGN 4.11, from which the host forms dh and dlower.
+template <class T, class Mat, bool kBackward, bool kRange, class P>
 QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, const P& g)
 {
+    static_assert(kBackward || !kRange, "the range role is a role of the backward");
     constexpr int M8 = Mat::MP, NT = Mat::NT;
     const int n = a.n, m = a.m, q = a.q;
     const FacLayout lay = fac_layout(n, m, q, a.images);
@@ -1513,6 +1869,7 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
     const In<T> ryg(q > 0 ? (kBackward ? a.dl_dnu : a.ry) : nullptr, (size_t)qp * q, io32);
     const In<T> lamg(kBackward ? a.lam : nullptr, (size_t)qp * m, io32), slg(kBackward ? a.slack : nullptr, (size_t)qp * m, io32);
     const In<T> dg(kBackward ? nullptr : a.d, (size_t)qp * m, io32);
+    const In<T> lamlg(kRange ? a.lam_lo : nullptr, (size_t)qp * m, io32), sllg(kRange ? a.slack_lo : nullptr, (size_t)qp * m, io32);
     bool jvp = false;                                  // forward mode (qpx_jvp): never in the backward's instantiation
     if constexpr (!kBackward) jvp = a.jvp != 0;
     // the backward with refinement keeps ry and rs/d - rz = -dl_dlam for the refinement's residuals where nu and lam will be
@@ -1540,6 +1897,10 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
             if (kBackward) {
                 const T l = lamg[i], sl = slg[i];
                 d = ((l < T(1e-8)) ? T(1e-8) : l) / ((sl < T(1e-8)) ? T(1e-8) : sl);      // qp.py:148
+                if constexpr (kRange) {      // ... of the doubled QP's lower row as well (0 on a one-sided row: slack_lo = +inf)
+                    const T ll = lamlg[i], sll = sllg[i];
+                    d += ((ll < T(1e-8)) ? T(1e-8) : ll) / ((sll < T(1e-8)) ? T(1e-8) : sll);
+                }
             } else {
                 d = dg[i];
             }
@@ -1672,7 +2033,8 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
         if (a.dp) put_(a.dp, io32, (size_t)qp * n + i, vDX[i]);
     }
     for (int i = b.tid; i < m; i += NT) {
-        vLM[i] = lamg[i];
+        if constexpr (kRange) vLM[i] = lamg[i] - lamlg[i];
+        else vLM[i] = lamg[i];
         if (a.dh) put_(a.dh, io32, (size_t)qp * m + i, -vDZ[i]);
     }
     for (int i = b.tid; i < q; i += NT) {
@@ -1710,12 +2072,12 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
     QPX_PROF_DUMP(F + lay.prof, T)          // (profiling build only: the blob's timer words, scripts/prof_backward.py)
 }
 
-template <class T, class Mat, bool kBackward>
+template <class T, class Mat, bool kBackward, bool kRange = false>
 QPX_DEV void kkt_mat_body(const Block& b, const KktArgs<T>& a, int qp, T* lds)
 {
     typename Mat::Pos g(b);
     g.assign(b, reinterpret_cast<int*>(lds));
-    Mat::with_role(g, [&](const auto& gp) { kkt_mat_role<T, Mat, kBackward>(b, a, qp, lds, gp); });
+    Mat::with_role(g, [&](const auto& gp) { kkt_mat_role<T, Mat, kBackward, kRange>(b, a, qp, lds, gp); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2114,11 +2476,12 @@ QPX_DEV void kkt_b2_body(const Block& b, const KktArgs<T>& a, int qp, T* lds)
 }
 
 // (NBL >= kKktMultiRole: the multi-right-hand-side role of the form with NBL - kKktMultiRole blocks, >= kKktB2Role: its
-// second-order role, qpx_forms.h)
+// second-order role, >= kKktRangeRole: the backward's range role, qpx_forms.h)
 template <class T, int GS, int NBL, bool kBackward>
 QPX_DEV void kkt_grid_body(const Block& b, const KktArgs<T>& a, int qp, T* lds)
 {
-    if constexpr (NBL >= kKktB2Role) kkt_b2_body<T, GridMat<T, GS, NBL - kKktB2Role>>(b, a, qp, lds);
+    if constexpr (NBL >= kKktRangeRole) kkt_mat_body<T, GridMat<T, GS, NBL - kKktRangeRole>, true, true>(b, a, qp, lds);
+    else if constexpr (NBL >= kKktB2Role) kkt_b2_body<T, GridMat<T, GS, NBL - kKktB2Role>>(b, a, qp, lds);
     else if constexpr (NBL >= kKktMultiRole) kkt_multi_body<T, GridMat<T, GS, NBL - kKktMultiRole>, kKktMultiRB>(b, a, qp, lds);
     else kkt_mat_body<T, GridMat<T, GS, NBL>, kBackward>(b, a, qp, lds);
 }

@@ -86,6 +86,11 @@ template <class T, int NBL, int NS> int launch_ipm_grid(const IpmArgs<T>& a, siz
 }
 #define QPX_INST(NBL, NS) template int launch_ipm_grid<QPX_TU_REAL, NBL, NS>(const IpmArgs<QPX_TU_REAL>&, size_t, void*);
 QPX_FORMS_IPM_GRID(QPX_INST)
+#if QPX_REAL_IS_DOUBLE
+// (NBL + kIpmRangeRole: the form's range role, qpx_ipm_range -- float64 arithmetic only)
+#define QPX_INSTR(NBL, NS) template int launch_ipm_grid<double, NBL + kIpmRangeRole, NS>(const IpmArgs<double>&, size_t, void*);
+QPX_FORMS_IPM_RANGE_GRID(QPX_INSTR)
+#endif
 #elif QPX_TU_KERNEL == 7
 // (NBL >= kKktMultiRole: the form's multi-right-hand-side role, >= kKktB2Role: its second-order role, qpx_forms.h)
 template <class T, int NBL, bool kBw> __global__ __launch_bounds__(256, (NBL % kKktMultiRole <= 7 ? 2 : 1)) void k_kkt_grid(KktArgs<T> a)
@@ -106,6 +111,9 @@ QPX_FORMS_KKT_GRID(QPX_INST)
 #if QPX_REAL_IS_DOUBLE
 #define QPX_INSTB2(NBL) template int launch_kkt_grid<double, kKktB2Role + NBL, false>(const KktArgs<double>&, size_t, void*);
 QPX_FORMS_KKT_GRID(QPX_INSTB2)
+// (kKktRangeRole + NBL: the backward's range role, qpx_backward_range)
+#define QPX_INSTBR(NBL) template int launch_kkt_grid<double, kKktRangeRole + NBL, true>(const KktArgs<double>&, size_t, void*);
+QPX_FORMS_KKT_GRID(QPX_INSTBR)
 #endif
 // the finishing stage (qpx_polish) on the thread grid
 template <class T, int NBL> __global__ __launch_bounds__(256) void k_polish_grid(PolishArgs<T> a)
@@ -220,15 +228,19 @@ template <int NBL, int NW, bool kBw, bool CH> int launch_kkt_tile(const KktArgs<
     template int launch_kkt_tile<NBL, NW, true, CH>(const KktArgs<double>&, size_t, void*);        \
     template int launch_kkt_tile<kKktMultiRole + NBL, NW, false, CH>(const KktArgs<double>&, size_t, void*);
 #define QPX_INSTKB2(NBL, NW, CH) template int launch_kkt_tile<kKktB2Role + NBL, NW, false, CH>(const KktArgs<double>&, size_t, void*);
+#define QPX_INSTKR(NBL, NW, CH) template int launch_kkt_tile<kKktRangeRole + NBL, NW, true, CH>(const KktArgs<double>&, size_t, void*);
 #if !defined(QPX_TILE_ONLY)
 QPX_FORMS_KKT_TILE(QPX_INSTK)
 QPX_FORMS_KKT_B2_TILE(QPX_INSTKB2)
+QPX_FORMS_KKT_RANGE_TILE(QPX_INSTKR)
 #endif
 #define QPX_INSTT(NBL, NW, NS, CH) template int launch_ipm_tile<NBL, NW, NS, CH>(const IpmArgs<double>&, size_t, void*);
 #if defined(QPX_TILE_ONLY)
 QPX_INSTT(7, QPX_TILE_ONLY, 2, QPX_TILE_ONLY == 4)
 #else
 QPX_FORMS_IPM_TILE(QPX_INSTT)
+#define QPX_INSTTR(NBL, NW, NS, CH) template int launch_ipm_tile<NBL + kIpmRangeRole, NW, NS, CH>(const IpmArgs<double>&, size_t, void*);
+QPX_FORMS_IPM_RANGE_TILE(QPX_INSTTR)
 #endif
 #endif
 

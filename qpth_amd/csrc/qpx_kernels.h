@@ -170,6 +170,13 @@ template <class T> struct IpmArgs {
     const T *lam0 = nullptr, *s0 = nullptr;
     T warm_floor = T(0);
     int* warm_used = nullptr;
+    // two-sided rows (qpx_ipm_range; the forms of kIpmRangeRole only): lower (B,m), batch stride slo (0 = shared), -inf = a
+    // one-sided row; gt1 (B) = || G^T e ||, e_i = 1 on the one-sided rows, NULL = 0; lam_lo, slack_lo (B,m): the lower side's
+    // multipliers and slacks beside lam, slack (0 and +inf on a one-sided row)
+    const T* lower = nullptr;
+    long long slo = 0;
+    const T* gt1 = nullptr;
+    T *lam_lo = nullptr, *slack_lo = nullptr;
 };
 
 template <class T> struct KktArgs {
@@ -202,6 +209,9 @@ template <class T> struct KktArgs {
     // the multi-right-hand-side role (qpx_factor_solve_kkt_multi, kkt_multi_role): K > 0 right-hand sides per QP -- rx, rs, rz,
     // ry and dx, ds, dz, dy are (B, K, .), a QP's K vectors contiguous; one d (B, m) and one factorisation for all of them
     int K = 0;
+    // the backward of two-sided rows (qpx_backward_range; the forms of kKktRangeRole only): the lower side's multipliers and
+    // slacks (B,m) -- d = clamp(lam)/clamp(slack) + clamp(lam_lo)/clamp(slack_lo), lam - lam_lo in the outer products
+    const T *lam_lo = nullptr, *slack_lo = nullptr;
 };
 
 // The finishing stage (qpx_polish, include/qpx.h): iterations of the reference's loop in the ORIGINAL variables

@@ -556,7 +556,8 @@ template <int NBL, int NW, bool CH = false> struct TileMat {
     // depends on the chain wave, so no barrier separates it from the mat-vec -- and the sixteen old rows of panel 0 -> X
     static constexpr int kPartA = kPart + NWM * NROW * 17;
     static_assert(!CH || (kPartA >= kBT + NBL * 256 && kPartA + NWM * NBL * 64 <= kRow), "kAhead: the column partials must survive the first operand tiles");
-    template <class P> static QPX_DEV void ahead_front(const Block& blk, const P& p0, Regs& E, const T* vin, const T* vz, const T* vs, T* scr)
+    // (kDiag -- the loop's range role: the diagonal itself arrives in vs, final since the previous pass ended)
+    template <bool kDiag = false, class P> static QPX_DEV void ahead_front(const Block& blk, const P& p0, Regs& E, const T* vin, const T* vz, const T* vs, T* scr)
     {
         if constexpr (role_of<P>::value >= 0) {
             const P p = p0.fresh();
@@ -598,7 +599,9 @@ template <int NBL, int NW, bool CH = false> struct TileMat {
 #pragma unroll
                 for (int J = 0; J < psize(pp); ++J) {
                     if (J != I) continue;
-                    const T d = vs[16 * J + p.c] * rcp_(vz[16 * J + p.c]);
+                    T d;
+                    if constexpr (kDiag) d = vs[16 * J + p.c];
+                    else d = vs[16 * J + p.c] * rcp_(vz[16 * J + p.c]);
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (p.c == p.g + 4 * r) E.e[slot(pp, J)][r] += d;
@@ -1310,9 +1313,9 @@ template <int NBL, int NW, bool CH = false> struct TileMat {
     }
 };
 
-QPX_LAYOUT_HD size_t lds_elems_ipm_tile(int nbl, int nw, int n, int q, bool chain = false)
+QPX_LAYOUT_HD size_t lds_elems_ipm_tile(int nbl, int nw, int n, int q, bool chain = false, bool range = false)
 {
-    return lds_elems_ipm_loop(16 * (size_t)nbl, tile_scratch_elems(nbl, chain ? nw - 1 : nw, chain), n, q);
+    return lds_elems_ipm_loop(16 * (size_t)nbl, tile_scratch_elems(nbl, chain ? nw - 1 : nw, chain), n, q, range);
 }
 
 QPX_LAYOUT_HD size_t lds_elems_kkt_tile(int nbl, int nw, int n, int q, bool chain = false)
@@ -1331,11 +1334,12 @@ QPX_LAYOUT_HD size_t lds_elems_kkt_b2_tile(int nbl, int nw, int n, int q, bool c
 }
 
 // (NBL >= kKktMultiRole: the multi-right-hand-side role of the form with NBL - kKktMultiRole tile rows, >= kKktB2Role: its
-// second-order role, qpx_forms.h)
+// second-order role, >= kKktRangeRole: the backward's range role, qpx_forms.h)
 template <int NBL, int NW, bool kBackward, bool CH = false>
 QPX_DEV void kkt_tile_body(const Block& b, const KktArgs<double>& a, int qp, double* lds)
 {
-    if constexpr (NBL >= kKktB2Role) kkt_b2_body<double, TileMat<NBL - kKktB2Role, NW, CH>>(b, a, qp, lds);
+    if constexpr (NBL >= kKktRangeRole) kkt_mat_body<double, TileMat<NBL - kKktRangeRole, NW, CH>, true, true>(b, a, qp, lds);
+    else if constexpr (NBL >= kKktB2Role) kkt_b2_body<double, TileMat<NBL - kKktB2Role, NW, CH>>(b, a, qp, lds);
     else if constexpr (NBL >= kKktMultiRole) kkt_multi_body<double, TileMat<NBL - kKktMultiRole, NW, CH>, kKktMultiRB>(b, a, qp, lds);
     else kkt_mat_body<double, TileMat<NBL, NW, CH>, kBackward>(b, a, qp, lds);
 }
@@ -1353,7 +1357,9 @@ QPX_LAYOUT_HD size_t lds_elems_centre_tile(int nbl, int n, int q, bool chain)
 template <int NBL, int NW, int NS, bool CH = false>
 QPX_DEV void ipm_tile_body(const Block& b, const IpmArgs<double>& a, int qp, double* lds)
 {
-    ipm_loop_body<double, TileMat<NBL, NW, CH>, NS>(b, a, qp, lds);
+    // (NBL >= kIpmRangeRole: the range role of the form with NBL - kIpmRangeRole tile rows, qpx_forms.h)
+    if constexpr (NBL >= kIpmRangeRole) ipm_loop_body<double, TileMat<NBL - kIpmRangeRole, NW, CH>, NS, true>(b, a, qp, lds);
+    else ipm_loop_body<double, TileMat<NBL, NW, CH>, NS>(b, a, qp, lds);
 }
 
 }  // namespace qpx

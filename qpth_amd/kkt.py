@@ -34,7 +34,8 @@ def default_stall_policy(B):
 
 class IpmResult:
     __slots__ = ("zhat", "nu", "lam", "slacks", "iters", "status", "best_resid", "trace", "_warm_used",
-                 "centre_resid", "centre_steps")         # the last two: set by KKTFactors.centre only
+                 "centre_resid", "centre_steps",         # these two: set by KKTFactors.centre only
+                 "lam_lo", "slacks_lo")                  # ... and these by KKTFactors.ipm_range only
 
     @property
     def warm_used(self):
@@ -118,6 +119,19 @@ def as_kappa(kappa, Q, nineq, nBatch=1):
             or (kappa.dim() == 2 and nBatch > 1 and kappa.size(0) != nBatch)):
         raise ValueError("qpth_amd: kappa has shape %s; expected (nBatch, %d), (%d,) or ()" % (tuple(kappa.shape), nineq, nineq))
     return kappa
+
+
+def as_lower(lower, Q, nineq, nBatch=1):
+    """The lower bounds of two-sided rows as every entry point takes them, as as_rho takes shapes: a tensor of Q's
+    dtype and device, shape (nBatch, nineq) or (nineq,) (shared by the batch); -inf = a one-sided row.  Raises ValueError
+    otherwise; the VALUES (below h, not NaN, not +inf) are checked by the loop kernel."""
+    if not torch.is_tensor(lower):
+        raise ValueError("qpth_amd: lower must be a tensor of shape (nBatch, %d) or (%d,)" % (nineq, nineq))
+    if lower.dtype != Q.dtype or lower.device != Q.device:
+        raise ValueError("qpth_amd: lower is %s on %s, the QP is %s on %s" % (lower.dtype, lower.device, Q.dtype, Q.device))
+    if lower.dim() not in (1, 2) or lower.size(-1) != nineq or (lower.dim() == 2 and nBatch > 1 and lower.size(0) != nBatch):
+        raise ValueError("qpth_amd: lower has shape %s; expected (nBatch, %d) or (%d,)" % (tuple(lower.shape), nineq, nineq))
+    return lower
 
 
 class _PinnedPool:
@@ -301,7 +315,22 @@ class KKTFactors:
         mask = _lib.ST_Q_NOT_SPD | _lib.ST_A_RANK
         if self.soft:
             mask |= _lib.ST_NONFINITE
-        if self._pre_soft is not None:
+        bad_lower = False
+        rng, self._range = getattr(self, "_range", None), None
+        if rng is not None:
+            # two-sided rows: the words ipm_range copied in FRONT of its loop launch -- the pre-factorisation's status and, per
+            # QP, whether a lower entry is NaN, +inf or not below its h (the loop's own test, formed by torch operations): they
+            # stand in for the read-back of the pre-factorisation's words, and the host still never waits for the loop
+            host, ev = rng
+            if ev is not None:
+                ev.synchronize()
+            words = host.cpu().numpy()
+            self._pre_bits = int(np.bitwise_or.reduce(words[0]))      # (a later call reads these, not the pinned buffer)
+            st = self._pre_bits & mask
+            bad_lower = bool(words[1].any())
+            if self._pre_host is not None:
+                self._release_pinned(False)
+        elif self._pre_soft is not None:
             st = int(np.bitwise_or.reduce(self._pre_soft.cpu().numpy().reshape(-1))) & mask
         elif self._pre_event is not None:
             if self._pre_bits is None:         # first reading: wait for the copy, keep the bits, free the buffer
@@ -324,6 +353,8 @@ a non-zero diagonal.
                                "the equality constraints must have full row rank.")
         if st & _lib.ST_NONFINITE:
             raise ValueError("rho must be positive")
+        if bad_lower:
+            raise ValueError("lower must be below h")
 
     def _no_refine_on_soft(self, refine, what):
         """refinement evaluates residuals from the caller's Q, G, A: of the HARD QP"""
@@ -399,6 +430,153 @@ a non-zero diagonal.
                          stall_policy, r.zhat, r.nu if q else None, r.lam, r.slacks, r.iters, self.status,
                          r.best_resid, r.trace, wide=self.wide, **kw)
         return r
+
+    # -- two-sided rows lower <= G z <= h ---------------------------------------
+    def range_ok(self):
+        """do qpx_ipm_range / qpx_backward_range serve these factors (under the knob they were built with)?  float64 tensors,
+        the thread-grid / tile kernels' sizes (nz+neq+nineq <= 208), no soft rows"""
+        if self.soft or self.wide or self.dtype != torch.float64 or not hasattr(self.lib.dll, "qpx_range_supported"):
+            return False
+        with self._knob():
+            return bool(self.lib.dll.qpx_range_supported(_lib.QPX_F64, self.n, self.m, self.q))
+
+    def _range_refusal(self):
+        return ValueError("qpth_amd: two-sided rows (lower) are served for float64 tensors up to nz + neq + nineq = 208 under the "
+                          "default knob, on hard factors; got %s, nz = %d, nineq = %d, neq = %d%s.  Write the rows as "
+                          "[G; -G] z <= [h; -lower] instead" % (str(self.dtype).replace("torch.", ""), self.n, self.m, self.q,
+                                                                ", soft rows" if self.soft else ""))
+
+    def gt1_of(self, lower, h):
+        """|| G^T e ||_2 per QP, e = 1 on the one-sided rows (h - lower = +inf, the kernel's test): the doubled QP's
+        || G'^T 1 || of the stop rule.  torch operations, no host sync; ONE number for the batch when G, h and lower are shared."""
+        G = self.G
+        if h.dim() == 2 and (h.size(0) == 1 or h.stride(0) == 0):
+            h = h[0]
+        # (broadcast: an h per QP beside a shared lower gives an e per QP -- the kernel's test row by row, also where
+        # h - lower overflows to +inf for a finite lower)
+        e = torch.isinf(h - lower).to(self.dtype)
+        if G.dim() == 3 and (G.size(0) == 1 or G.stride(0) == 0):
+            G = G[0]
+        if e.dim() == 2 and (e.size(0) == 1 or e.stride(0) == 0):
+            e = e[0]
+        if G.dim() == 2 and e.dim() == 1:
+            return torch.linalg.vector_norm(e @ G).reshape(1).expand(self.B).contiguous()
+        g = torch.matmul(e.unsqueeze(-2), G).squeeze(-2)
+        return torch.linalg.vector_norm(g, dim=-1).expand(self.B).contiguous()
+
+    def ipm_range(self, p, h, lower, b, eps=1e-12, maxIter=20, notImprovedLim=3, stall_policy=None, want_trace=False):
+        """The IPM loop for  lower <= G z <= h  in nineq rows (qpx_ipm_range): the iterates of ipm() on the doubled QP
+        [G; -G_F] z <= [h; -lower_F], one launch, no host sync.  lower (B, nineq), (1, nineq) or (nineq,); -inf = a one-sided
+        row.  The result has lam, slacks of the rows G z <= h and lam_lo, slacks_lo of lower <= G z (0 and +inf on a one-sided
+        row).  A lower entry that is NaN, +inf or not below its h: QPX_ST_NONFINITE in `status` (raise_on_failure)."""
+        if not self.range_ok():
+            raise self._range_refusal()
+        B, n, m, q = self.B, self.n, self.m, self.q
+        dt, dev = self.dtype, self.device
+        self._check(p, n, "p")
+        self._check(h, m, "h")
+        self._check(lower, m, "lower")
+        if q:
+            if b is None or b.nelement() == 0:
+                raise RuntimeError("qpth_amd: A has %d rows but b is empty" % q)
+            self._check(b, q, "b")
+        r = IpmResult()
+        r.zhat = torch.empty(B, n, dtype=dt, device=dev)
+        r.nu = torch.empty(B, q, dtype=dt, device=dev)
+        r.lam = torch.empty(B, m, dtype=dt, device=dev)
+        r.slacks = torch.empty(B, m, dtype=dt, device=dev)
+        r.lam_lo = torch.empty(B, m, dtype=dt, device=dev)
+        r.slacks_lo = torch.empty(B, m, dtype=dt, device=dev)
+        r.iters = torch.empty(B, dtype=torch.int32, device=dev)
+        r.best_resid = torch.empty(B, dtype=dt, device=dev)
+        r.trace = torch.full((maxIter, B, 3), float('nan'), dtype=dt, device=dev) if want_trace else None
+        # the status words of THIS launch: a copy of the pre-factorisation's that the loop ORs its bits into -- a bad lower's
+        # QPX_ST_NONFINITE stays with the launch that met it, the factors' own words never see it
+        r.status = self.status.clone()
+        r._warm_used = None
+        # ... and what raise_on_failure reads: copied to pinned memory in front of the loop launch (no stream capture: there
+        # the words stay on the device and are read from it)
+        bad = (~(lower.detach() < h.detach())).any(-1).expand(B).to(torch.int32)
+        words = torch.stack((self.status, bad))
+        if words.is_cuda and not torch.cuda.is_current_stream_capturing():
+            host = torch.empty(words.shape, dtype=torch.int32, pin_memory=True)
+            host.copy_(words, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            self._range = (host, ev)
+        else:
+            self._range = (words, None)
+        if stall_policy is None:
+            stall_policy = default_stall_policy(B)
+        gt1 = self.gt1_of(lower.detach(), h.detach())
+        with self._knob():
+            self.lib.ipm_range(B, n, m, q, p, h, lower, gt1, b if q else None, self.blob, self.sfac, eps, maxIter,
+                               notImprovedLim, stall_policy, r.zhat, r.nu if q else None, r.lam, r.slacks, r.lam_lo,
+                               r.slacks_lo, r.iters, r.status, r.best_resid, r.trace)
+        return r
+
+    def backward_range(self, zhat, lam, slacks, lam_lo, slacks_lo, nu, dl_dz, want=(True,) * 7, shared=(False,) * 7):
+        """Gradients (dQ, dp, dG, dh, dA, db, dlower) of a loss on zhat for the rows lower <= G z <= h, as backward(): `want`
+        and `shared` have a seventh entry for lower.  One launch (qpx_backward_range): the backward's KKT solve with
+        d = du + dl, du = clamp(lam)/clamp(slacks), dl = clamp(lam_lo)/clamp(slacks_lo), and lam - lam_lo in dG; from its
+        dz = v the two bounds' gradients dh = -v du/(du + dl), dlower = -v dl/(du + dl) (exactly 0 on a one-sided row) are
+        elementwise operations here, as drho is."""
+        if not self.range_ok():
+            raise self._range_refusal()
+        B, n, m, q = self.B, self.n, self.m, self.q
+        dt, dev = self.dtype, self.device
+        wQ, wp, wG, wh, wA, wb, wl = [bool(w) for w in want]
+        sQ, sp, sG, sh, sA, sb, sl = [bool(s) for s in shared]
+        if q == 0:
+            wA = wb = False
+
+        def buf(flag, *shape):
+            return torch.empty(*shape, dtype=dt, device=dev) if flag else None
+
+        dQ = buf(wQ and not sQ, B, n, n)
+        dG = buf(wG and not sG, B, m, n)
+        dA = buf(wA and not sA, B, q, n)
+        dp = buf(wp and not sp, B, n)
+        db = buf(wb and not sb, B, q)
+        dx = buf((wp and sp) or (wQ and sQ) or (wG and sG) or (wA and sA), B, n)
+        dz = buf(wh or wl or (wG and sG), B, m)
+        dy = buf(q > 0 and ((wb and sb) or (wA and sA)), B, q)
+        zh, lm, nv = self._vec(zhat, n, "zhat"), self._vec(lam, m, "lam"), self._vec(nu, q, "nu")
+        ll, sll = self._vec(lam_lo, m, "lam_lo"), self._vec(slacks_lo, m, "slacks_lo")
+        sk = self._vec(slacks, m, "slacks")
+        gz = self._vec(dl_dz, n, "dl_dz")
+        if gz is None:
+            raise RuntimeError("qpth_amd: backward_range needs dl_dz")
+        with self._knob():
+            self.lib.backward_range(B, n, m, q, self.blob, self.sfac, zh, lm, sk, ll, sll, nv, gz, dQ, dp, dG, dA, db,
+                                    self.status, dx, dz, dy)
+            if wQ and sQ:
+                dQ = torch.empty(n, n, dtype=dt, device=dev)
+                self.lib.batch_outer(dx, zh, zh, dx, 0.5, dQ)
+            if wG and sG:
+                dG = torch.empty(m, n, dtype=dt, device=dev)
+                self.lib.batch_outer(dz, zh, lm - ll, dx, 1.0, dG)
+            if wA and sA:
+                dA = torch.empty(q, n, dtype=dt, device=dev)
+                self.lib.batch_outer(dy, zh, nv, dx, 1.0, dA)
+            if wp and sp:
+                dp = torch.empty(n, dtype=dt, device=dev)
+                self.lib.batch_outer(dx, None, None, None, 1.0, dp)
+            if wb and sb:
+                db = torch.empty(q, dtype=dt, device=dev)
+                self.lib.batch_outer(dy, None, None, None, -1.0, db)
+        dh = dlo = None
+        if wh or wl:
+            du = lm.clamp(min=1e-8) / sk.clamp(min=1e-8)
+            dl = ll.clamp(min=1e-8) / sll.clamp(min=1e-8)
+            share = dl / (du + dl)
+            if wh:
+                dh = dz * (share - 1.0)
+                dh = dh.mean(0) if sh else dh
+            if wl:
+                dlo = -dz * share
+                dlo = dlo.mean(0) if sl else dlo
+        return dQ, dp, dG, dh, dA, db, dlo
 
     # -- factor_kkt + solve_kkt (batch.py:435-470, 349-372) ----------------------------------
     def solve_kkt(self, d, rx, rs, rz, ry, refine=0):

@@ -17,6 +17,8 @@ The backward is itself differentiable once: torch.autograd.grad(..., create_grap
 products through the layer, one more launch with one factorisation and two solves (qpx_backward2).
 QPFunction(...)(Q, p, G, h, A, b, kappa=kappa) returns the point of the CENTRAL PATH at kappa instead of the solution -- the
 log-barrier smoothing of the QP, C-infinity in all parameters and in kappa; one more launch in the forward (qpx_centre).
+QPFunction(...)(Q, p, G, h, A, b, lower=l) solves  l <= Gz <= h  in nineq rows -- not [G; -G] z <= [h; -l] in 2 nineq --, differentiable
+in l as well: the loop's and the backward's range role, the same number of launches (qpx_ipm_range).
 """
 from enum import Enum
 
@@ -25,7 +27,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .kkt import KKTFactors, as_kappa, as_rho
+from .kkt import KKTFactors, as_kappa, as_lower, as_rho
 from .solvers.pdipm import batch as pdipm_b
 from .util import expandParam, extract_nBatch
 
@@ -59,8 +61,20 @@ def f64_arithmetic_serves(nz, nineq, neq, lib=None):
 def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                maxIter=20, solver=QPSolvers.PDIPM_BATCHED,
                check_Q_spd=True, refine=None, duals=False, warm_start=None, kappa_tol=1e-9, kappa_steps=20):
-    """Returns f(Q, p, G, h, A, b, rho=None, kappa=None).  `refine`, `duals`, `warm_start` and the inputs `rho` and `kappa` are what
-    the reference does not have.
+    """Returns f(Q, p, G, h, A, b, rho=None, kappa=None, lower=None).  `refine`, `duals`, `warm_start` and the inputs `rho`, `kappa`
+    and `lower` are what the reference does not have.
+    lower: two-sided inequality rows,
+          min 1/2 z'Qz + p'z   s.t.  lower <= Gz <= h,  Az = b,
+      box and range constraints in nineq rows: the iterates, iteration counts and solution of the reference on the doubled QP
+      [G; -G] z <= [h; -lower], whose Newton system collapses to the nineq x nineq system the loop factors anyway -- the kernels'
+      cost is cubic in the rows, and a doubled box on 100 variables leaves the register-resident kernels altogether.  A tensor
+      of the other inputs' dtype and device, shape (nBatch, nineq) or (nineq,) (shared by the batch); -inf = a one-sided row,
+      so lower = -inf everywhere is the six-input QP.  A seventh differentiable input in reverse mode (d loss / d lower is
+      exactly 0 on a one-sided row); a shared lower gets the `.mean(0)` convention.  An entry that is NaN, +inf or not below
+      its h raises ValueError("lower must be below h") from the forward.  float64 inputs at sizes the thread-grid / tile
+      kernels serve (nz+neq+nineq <= 208) only; not together with rho, kappa, refine > 0, duals=True, warm_start, float32
+      inputs or solver=QPSolvers.CVXPY: each a ValueError from the call that names the doubled call as the way out.  Forward
+      mode and second derivatives are not served: RuntimeError.  lower=None is the call as before: the same nodes and launches.
     kappa: the barrier-smoothed QP.  The call returns the point of the central path
           Q z + p + G'lam + A'nu = 0,  G z + s = h,  A z = b,  s_i lam_i = kappa_i   (s, lam > 0),
       the minimiser of 1/2 z'Qz + p'z - sum_i kappa_i log(h_i - g_i'z) s.t. Az = b, instead of the QP's solution: smooth in all
@@ -396,6 +410,76 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         def backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
             return _backward(ctx, dl_dzhat, dl_dnu, dl_dlam, dl_dslacks)
 
+    class QPRangeFunctionFn(Function):
+        """the node of two-sided rows: lower, the seventh differentiable input, behind the six parameters"""
+        @staticmethod
+        def forward(ctx, Q_, p_, G_, h_, A_, b_, lower_):
+            nBatch = extract_nBatch(Q_, p_, G_, h_, A_, b_)
+            if lower_.dim() == 2:
+                nBatch = max(nBatch, lower_.size(0))
+            Q, _ = expandParam(Q_, nBatch, 3)
+            p, _ = expandParam(p_, nBatch, 2)
+            G, _ = expandParam(G_, nBatch, 3)
+            h, _ = expandParam(h_, nBatch, 2)
+            A, _ = expandParam(A_, nBatch, 3)
+            b, _ = expandParam(b_, nBatch, 2)
+            ctx.neq = A_.size(-2) if A_.nelement() > 0 else 0
+            fac = KKTFactors.build(Q, G, A, nBatch)
+            res = fac.ipm_range(p, h, lower_.detach(), b, eps, maxIter, notImprovedLim, want_trace=(verbose == 1))
+            # one small read-back: the reference raises here too (qp.py:81-85), and so does a lower entry not below its h
+            fac.raise_on_failure(check_Q_spd)
+            if verbose == 1:
+                _print_trace(res)
+            if verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
+                print(pdipm_b.INACC_ERR)
+            ctx.fac = fac
+            ctx.nus, ctx.lams, ctx.slacks, ctx.lams_lo, ctx.slacks_lo = res.nu, res.lam, res.slacks, res.lam_lo, res.slacks_lo
+            ctx.save_for_backward(res.zhat, Q_, p_, G_, h_, A_, b_, lower_)
+            return res.zhat
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            raise RuntimeError("qpth_amd: forward mode is not served with two-sided rows (lower); write the rows as "
+                               "[G; -G] z <= [h; -lower]")
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dl_dzhat):
+            zhats, Q, p, G, h, A, b, lower = ctx.saved_tensors
+            nBatch = max(extract_nBatch(Q, p, G, h, A, b), lower.size(0) if lower.dim() == 2 else 1)
+            shared = (Q.dim() == 2, p.dim() == 1, G.dim() == 2, h.dim() == 1, A.dim() == 2, b.dim() == 1, lower.dim() == 1)
+            grads = ctx.fac.backward_range(zhats, ctx.lams, ctx.slacks, ctx.lams_lo, ctx.slacks_lo, ctx.nus, dl_dzhat,
+                                           want=tuple(ctx.needs_input_grad[:7]), shared=shared)
+            if ctx.neq == 0:
+                grads = grads[:4] + (None, None) + grads[6:]
+            return grads
+
+    def _apply_range(Q, p, G, h, A, b, rho, kappa, lower):
+        what = "qpth_amd: lower (two-sided rows)"
+        out = "; write the rows as [G; -G] z <= [h; -lower] instead"
+        if rho is not None:
+            raise ValueError(what + " together with rho (soft rows) is not served" + out)
+        if kappa is not None:
+            raise ValueError(what + " together with kappa (the barrier-smoothed QP) is not served" + out)
+        if solver != QPSolvers.PDIPM_BATCHED:
+            raise ValueError(what + " is served by solver=QPSolvers.PDIPM_BATCHED only" + out)
+        if refine is not None and int(refine) > 0:
+            raise ValueError(what + " with refine=%d is not served: pass refine=0 or refine=None" % int(refine) + out)
+        if duals:
+            raise ValueError(what + " with duals=True is not served (the multipliers are no outputs of this node)" + out)
+        if warm_start is not None:
+            raise ValueError(what + " with warm_start is not served" + out)
+        if Q.dtype != torch.float64:
+            raise ValueError(what + " is served for float64 inputs only (the range role exists in float64 arithmetic), got %s"
+                             % Q.dtype + out)
+        nineq, nz = G.size(-2), G.size(-1)
+        neq = A.size(-2) if A.nelement() > 0 else 0
+        if not _lib.backend_for(Q).dll.qpx_range_supported(_lib.QPX_F64, nz, nineq, neq):
+            raise ValueError(what + " is served up to nz + neq + nineq = 208 (the thread-grid / tile kernels, qpx_range_supported); "
+                             "got nz = %d, nineq = %d, neq = %d" % (nz, nineq, neq) + out)
+        lower = as_lower(lower, Q, nineq, extract_nBatch(Q, p, G, h, A, b))
+        return QPRangeFunctionFn.apply(Q, p, G, h, A, b, lower)
+
     def _apply_smooth(Q, p, G, h, A, b, rho, kappa):
         what = "qpth_amd: kappa (the barrier-smoothed QP)"
         if rho is not None:
@@ -418,7 +502,9 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         kappa = as_kappa(kappa, Q, nineq, extract_nBatch(Q, p, G, h, A, b))
         return QPSmoothFunctionFn.apply(Q, p, G, h, A, b, kappa, loop_eps)
 
-    def apply(Q, p, G, h, A, b, rho=None, kappa=None):
+    def apply(Q, p, G, h, A, b, rho=None, kappa=None, lower=None):
+        if lower is not None:
+            return _apply_range(Q, p, G, h, A, b, rho, kappa, lower)
         if kappa is not None:
             return _apply_smooth(Q, p, G, h, A, b, rho, kappa)
         if rho is None:
