@@ -399,6 +399,35 @@ int qpx_backward_range(int dtype, int B, int n, int m, int q, void* factors, int
                        void* db, void* dx, void* dz, void* dy, int refine, const void* Q, int64_t sQ, const void* G, int64_t sG,
                        const void* A, int64_t sA, int32_t* status, const void* lam_lo, const void* slack_lo, qpx_stream_t stream);
 
+/* Additive after v8 (QPX_ABI_VERSION stays 8): ELASTIC inequality rows,
+ *   min 1/2 z'Qz + p'z + sum_i ( gamma_i t_i + 1/2 rho_i t_i^2 )   s.t.  G z <= h + t,  t >= 0,  A z = b
+ * -- the QP a caller had to write with nz + nineq variables and 2 nineq rows.  The factors are those of qpx_pre_factor for
+ * (Q, G, A), the HARD QP's: the augmented QP's Newton system collapses to the m x m system the loop already factors, with the
+ * diagonal s/lam + 1/(rho + lam_t/slack_t); the iterates, iteration counts and stop rule are those of qpx_ipm on the augmented QP.
+ * qpx_ipm_elastic: qpx_ipm's arguments, then
+ *   gamma, rho (B,m) of dtype, batch strides sgamma, srho in elements (0 = one (m) vector for the batch); a row with gamma = +inf
+ *     or rho = +inf is a HARD row, as in qpx_ipm; otherwise gamma >= 0 and rho > 0;
+ *   gt1 (B) of dtype: sqrt(|| G^T 1 ||^2 + 4 k) per QP, k its number of elastic rows -- the augmented QP's || G'^T 1 || of the
+ *     stop rule (batch.py:103-107);
+ *   lam_t, slack_t, t (B,m) of dtype, out: the multipliers and slacks of t >= 0 and t itself, beside lam, slack (= h + t - G z)
+ *     of the rows; 0, +inf and 0 on a hard row.
+ * status: a gamma entry that is NaN or negative, a rho entry that is NaN or not positive ORs QPX_ST_NONFINITE and the QP is left
+ * as after a failed pre-factorisation: NaN in the outputs, iters = 0, best_resid = +inf.  trace as in qpx_ipm; mu is the
+ * augmented QP's (over nineq + k).
+ * The derivative entry points serve the solution as they stand, on the same factors, given lam and the EFFECTIVE slack
+ *   slack_eff = clamp(lam) (1/du + 1/(rho + dt)),   du = clamp(lam)/clamp(slack), dt = clamp(lam_t)/clamp(slack_t)
+ * (slack on a hard row; clamps at 1e-8); with dz the inequality block of their KKT solution, dl/dgamma = dz/(dt + rho) and
+ * dl/drho = t dl/dgamma.  qpx_backward2 is NOT served that way.
+ * Served in float64 arithmetic by the loop forms the default dispatch picks, nz+neq+nineq <= 208 (qpx_elastic_supported);
+ * QPX_F32, QPX_F32_WIDE, the large-QP family and forms reachable through the A/B knob alone: QPX_ERR_UNSUPPORTED.  No warm
+ * start and no soft factors (qpx_pre_factor_soft) in this role. */
+int qpx_elastic_supported(int dtype, int n, int m, int q);
+int qpx_ipm_elastic(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
+                    const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
+                    int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
+                    void* best_resid, void* trace, const void* gamma, int64_t sgamma, const void* rho, int64_t srho,
+                    const void* gt1, void* lam_t, void* slack_t, void* t, qpx_stream_t stream);
+
 /* Batch-MEAN of the gradient of a parameter that the whole batch shares (qp.py:159-177: the reference
  * forms B outer products and then `.mean(0)`): one contraction over the batch instead,
  *   out (r,c) = scale/B * sum_b ( u[b][r] v[b][c] + w[b][r] x[b][c] )        u, w: (B,r)  v, x: (B,c)

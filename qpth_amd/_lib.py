@@ -72,6 +72,9 @@ _SIGNATURES = {
                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "qpx_backward_range": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "qpx_elastic_supported": (_i, [_i, _i, _i, _i]),
+    "qpx_ipm_elastic": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d, _i, _i, _i,
+                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "qpx_batch_outer": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, ctypes.c_size_t, _vp]),
     "qpx_batch_outer_workspace_elems": (ctypes.c_size_t, [_i, _i, _i, _i]),
     "qpx_dense_solve": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -251,6 +254,17 @@ class QpxLib:
             _dtype_code(factors), B, n, m, q, _ptr(factors), int(sfac), _ptr(zhat), _ptr(lam), _ptr(slack), _ptr(nu),
             _ptr(dl_dz), _ptr(dQ), _ptr(dp), _ptr(dG), None, _ptr(dA), _ptr(db), _ptr(dx), _ptr(dz), _ptr(dy), 0,
             None, 0, None, 0, None, 0, _ptr(status), _ptr(lam_lo), _ptr(slack_lo), _stream(factors)))
+
+    # -- elastic rows G z <= h + t, t >= 0: the loop's elastic role, float64
+    def ipm_elastic(self, B, n, m, q, p, h, gamma, rho, gt1, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
+                    zhat, nu, lam, slack, lam_t, slack_t, t, iters, status, best_resid, trace=None):
+        """gamma, rho (B,m), (1,m) or (m,) (shared: batch stride 0), +inf in either = a hard row; gt1 (B,) = || G'^T 1 ||"""
+        pp, hp, bp, gp, rp = Param(p, 2), Param(h, 2), Param(b, 2), Param(gamma, 2), Param(rho, 2)
+        self.check(self.dll.qpx_ipm_elastic(
+            _dtype_code(factors), B, n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
+            _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
+            _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid), _ptr(trace),
+            gp.ptr, gp.stride, rp.ptr, rp.stride, _ptr(gt1), _ptr(lam_t), _ptr(slack_t), _ptr(t), _stream(factors)))
 
     # -- forward mode (QPFunctionFn.jvp): the tangent of the solution, one KKT solve with the backward's matrix
     def jvp(self, B, n, m, q, factors, sfac, zhat, lam, slack, nu, tQ, tp, tG, th, tA, tb, dzhat, status,

@@ -428,7 +428,7 @@ inline int api_ipm_range(IpmArgs<double>& a, void* stream, bool launch)
         const int nst = slots_for(n, 16 * nbt, q);
         const int nw = tile_waves(nbt, a.B);
         const bool ch = tile_chain(nbt, nw);
-        const size_t tb = lds_elems_ipm_tile(nbt, nw, n, q, ch, true) * sizeof(double);
+        const size_t tb = lds_elems_ipm_tile(nbt, nw, n, q, ch, 1) * sizeof(double);
         if (tb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
 #define QPX_PICK(NBL, NW, NS, CH) \
         if (nbt == NBL && nw == NW && nst == NS && ch == CH) return launch ? launch_ipm_tile<NBL + kIpmRangeRole, NW, NS, CH>(a, tb, stream) : QPX_OK;
@@ -438,7 +438,7 @@ inline int api_ipm_range(IpmArgs<double>& a, void* stream, bool launch)
     }
     const int nbg = grid_nb(m);
     const int nsg = slots_for(n, 16 * nbg, q);
-    const size_t gb = lds_elems_ipm_grid(16, nbg, n, q, true) * sizeof(double);
+    const size_t gb = lds_elems_ipm_grid(16, nbg, n, q, 1) * sizeof(double);
     if (gb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
 #define QPX_PICK(NBL, NS) if (nbg == NBL && nsg == NS) return launch ? launch_ipm_grid<double, NBL + kIpmRangeRole, NS>(a, gb, stream) : QPX_OK;
     QPX_FORMS_IPM_RANGE_GRID(QPX_PICK)
@@ -476,6 +476,44 @@ inline bool range_served(int dtype, int n, int m, int q, int B)
     KktArgs<double> ka{};
     ka.B = B; ka.n = n; ka.m = m; ka.q = q;
     return api_ipm_range(ia, nullptr, false) == QPX_OK && api_backward_range(ka, nullptr, false) == QPX_OK;
+}
+
+// Elastic rows (qpx_ipm_elastic; DESIGN 4.12): the elastic role of the same loop forms (qpx_forms.h: kIpmElasticRole), picked by
+// api_ipm_range's rule; the backward runs on the hard factors as it stands.  A form without the role declines.
+inline int api_ipm_elastic(IpmArgs<double>& a, void* stream, bool launch)
+{
+    const int n = a.n, m = a.m, q = a.q;
+    if (!use_grid(n, m, q)) return QPX_ERR_UNSUPPORTED;            // the large-QP family has no such role
+    a.images = blob_images<double>(n, m, q);
+    if (a.images == 4) {
+        const int nbt = tile_nb(m);
+        const int nst = slots_for(n, 16 * nbt, q);
+        const int nw = tile_waves(nbt, a.B);
+        const bool ch = tile_chain(nbt, nw);
+        const size_t tb = lds_elems_ipm_tile(nbt, nw, n, q, ch, 2) * sizeof(double);
+        if (tb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
+#define QPX_PICK(NBL, NW, NS, CH) \
+        if (nbt == NBL && nw == NW && nst == NS && ch == CH) return launch ? launch_ipm_tile<NBL + kIpmElasticRole, NW, NS, CH>(a, tb, stream) : QPX_OK;
+        QPX_FORMS_IPM_RANGE_TILE(QPX_PICK)
+#undef QPX_PICK
+        return QPX_ERR_UNSUPPORTED;
+    }
+    const int nbg = grid_nb(m);
+    const int nsg = slots_for(n, 16 * nbg, q);
+    const size_t gb = lds_elems_ipm_grid(16, nbg, n, q, 2) * sizeof(double);
+    if (gb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
+#define QPX_PICK(NBL, NS) if (nbg == NBL && nsg == NS) return launch ? launch_ipm_grid<double, NBL + kIpmElasticRole, NS>(a, gb, stream) : QPX_OK;
+    QPX_FORMS_IPM_RANGE_GRID(QPX_PICK)
+#undef QPX_PICK
+    return QPX_ERR_UNSUPPORTED;
+}
+// (B: the batch the tile forms' waves per QP depend on)
+inline bool elastic_served(int dtype, int n, int m, int q, int B)
+{
+    if (dtype != QPX_F64) return false;
+    IpmArgs<double> ia{};
+    ia.B = B; ia.n = n; ia.m = m; ia.q = q;
+    return api_ipm_elastic(ia, nullptr, false) == QPX_OK;
 }
 
 // the finishing stage: every family has it (thread-grid / tile kernels: one kernel, the blob's register image of R decides the
@@ -914,6 +952,39 @@ int qpx_backward_range(int dtype, int B, int n, int m, int q, void* factors, int
     a.dx = (double*)dx; a.dz = (double*)dz; a.dy = (double*)dy;
     a.status = status;
     return qpx::api_backward_range(a, stream, true);
+}
+
+int qpx_elastic_supported(int dtype, int n, int m, int q)
+{
+    if (qpx::check_dims(dtype, 1, n, m, q) != QPX_OK) return 0;
+    // (a small and a large batch cover both choices of the tile forms' waves per QP)
+    return qpx::elastic_served(dtype, n, m, q, 1) && qpx::elastic_served(dtype, n, m, q, 1 << 20) ? 1 : 0;
+}
+
+int qpx_ipm_elastic(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
+                    const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
+                    int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
+                    void* best_resid, void* trace, const void* gamma, int64_t sgamma, const void* rho, int64_t srho,
+                    const void* gt1, void* lam_t, void* slack_t, void* t, qpx_stream_t stream)
+{
+    const int e = qpx::check_dims(dtype, B, n, m, q);
+    if (e) return e;
+    if (!p || !h || !gamma || !rho || !gt1 || !factors || !zhat || !lam || !slack || !lam_t || !slack_t || !t || !iters || !status ||
+        !best_resid || (q > 0 && (!nu || !b)))
+        return QPX_ERR_ARG;
+    if (maxIter < 0 || stall_policy < 0 || stall_policy > 2 || sgamma < 0 || srho < 0) return QPX_ERR_ARG;
+    if (!qpx::elastic_served(dtype, n, m, q, B)) return QPX_ERR_UNSUPPORTED;
+    qpx::IpmArgs<double> a{};
+    a.B = B; a.n = n; a.m = m; a.q = q;
+    a.p = (const double*)p; a.h = (const double*)h; a.b = (const double*)b;
+    a.sp = sp; a.sh = sh; a.sb = sb;
+    a.fac = (double*)factors; a.fac_stride = (size_t)sfac;
+    a.eps = eps; a.maxIter = maxIter; a.notImprovedLim = notImprovedLim; a.stall_policy = stall_policy;
+    a.zhat = (double*)zhat; a.nu = (double*)nu; a.lam = (double*)lam; a.slack = (double*)slack;
+    a.iters = iters; a.status = status; a.best_resid = (double*)best_resid; a.trace = (double*)trace;
+    a.gamma = (const double*)gamma; a.sgamma = sgamma; a.rho = (const double*)rho; a.srho = srho; a.gt1 = (const double*)gt1;
+    a.lam_lo = (double*)lam_t; a.slack_lo = (double*)slack_t; a.tviol = (double*)t;
+    return qpx::api_ipm_elastic(a, stream, true);
 }
 
 int qpx_polish_supported(int dtype, int n, int m, int q)

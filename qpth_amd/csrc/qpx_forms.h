@@ -55,6 +55,13 @@ constexpr int kPolishCentreRole = 64;
 constexpr int kIpmRangeRole = 64;
 constexpr int kKktRangeRole = 256;
 
+// Elastic rows G z <= h + t, t >= 0 with the penalty gamma't + 1/2 t'diag(rho)t (qpx_ipm_elastic), float64 arithmetic
+// only.  The loop forms of QPX_FORMS_IPM_RANGE_TILE / _GRID exist a third time as the ELASTIC role (qpx_grid.h: ipm_loop_role,
+// kElastic): blocks / tile rows + kIpmElasticRole in the form's FIRST parameter, decoded where the range role is; the one-sided
+// and the range forms hold none of its code.  The backward has no such role: it runs on the hard factors with an effective
+// slack the host forms.
+constexpr int kIpmElasticRole = 128;
+
 }  // namespace qpx
 
 // thread-grid kernels: (blocks of 16 -- of 8 in the one-wave grid -- per side), (blocks, slots of 64 columns)

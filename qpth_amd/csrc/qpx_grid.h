@@ -274,17 +274,17 @@ template <class T, int GS, int NBL> struct GridMat {
 
 // LDS elements of the loop kernel: 17 vectors of v = 64 NS >= max(n, MP, q), 16 scalars + 8 control
 // words, scratch
-// (range role: ten more vectors, the lower side's -- ipm_loop_role)
-QPX_LAYOUT_HD size_t lds_elems_ipm_loop(size_t mp, size_t scratch, int n, int q, bool range = false)
+// (role 1, the range role: ten more vectors, the lower side's; role 2, the elastic role: eleven, t's side -- ipm_loop_role)
+QPX_LAYOUT_HD size_t lds_elems_ipm_loop(size_t mp, size_t scratch, int n, int q, int role = 0)
 {
     const size_t d = max2(max2((size_t)n, mp), (size_t)q);
     const size_t v = d <= 64 ? 64 : (d <= 128 ? 128 : (d <= 256 ? 256 : 512));    // 64 NS, see ipm_loop_body
-    return (range ? 27 : 17) * v + 24 + scratch;
+    return (role == 2 ? 28 : (role == 1 ? 27 : 17)) * v + 24 + scratch;
 }
-QPX_LAYOUT_HD size_t lds_elems_ipm_grid(int gs, int nbl, int n, int q, bool range = false)
+QPX_LAYOUT_HD size_t lds_elems_ipm_grid(int gs, int nbl, int n, int q, int role = 0)
 {
     const size_t mg = (size_t)gs * nbl;
-    return lds_elems_ipm_loop(mg, 2 * mg + 4 + (size_t)nbl * gs * gs, n, q, range);
+    return lds_elems_ipm_loop(mg, 2 * mg + 4 + (size_t)nbl * gs * gs, n, q, role);
 }
 
 // out[c] (op)= sum_r Mat[r][c] * vec[r]   -- thread per column c: the loads of a row are
@@ -1117,13 +1117,212 @@ QPX_DEV void range_final_step(const Block& b, int lane, int m, const T* vH, T* v
 }
 
 // ------------------------------------------------------------------------------------------
+// The same blocks for ELASTIC rows g_i'z <= h_i + t_i, t_i >= 0 with the penalty gamma_i t_i + 1/2 rho_i t_i^2 (the loop's elastic
+// role).  The reference's QP has the variables (z, t_F) and the rows [G, -E; 0, -I] (z, t) <= (h, 0) (F: the rows
+// with finite gamma and rho); with wu = zu/su, wt = zt/st and e = 1/(rho + wt) its Newton system (R' + D'^-1) dz' = -(qu, qt)
+// collapses to the m x m system of the one-sided loop,
+//   (R + diag(1/wu + e)) dzu = -(qu - wt e qt),   dzt = -wt e (rho qt + dzu),   ds_t = -g_t + e (rho qt + dzu)
+// (g_t: what stands for g in ds = -g - dz/w of that step), and 1/rho appears in t = (zu' + zt' - gamma)/rho alone:
+// affine step   qu = c + R zu + t, rho qt = zu + zt - gamma, so the right-hand side is (c + R zu) + e (zu + zt - gamma);
+// corrector     qu = rsu/wu, qt = rst/wt: right-hand side rsu/wu - e rst, dzt = -e (rho rst + wt dzu), ds_t = -e (rst - dzu).
+// None of these is a small difference of large numbers on a row whose wu or wt is ~ 1/mu.  t's side is LDS vectors beside the
+// upper side's; vRho marks the rows: finite on F, +inf on a hard row, which runs the one-sided row's very operations
+// (zt = 0, st = +inf are only ever written out).  1/z, 1/s of both sides and vD = 1/wu + e are formed where z and s are, as in
+// the range role.
+template <class T> QPX_DEV bool elastic_(T rho) { return rho < Lim<T>::inf(); }
+// the reciprocals and the diagonal of the iterate (zu, su, zt, st) of row i
+template <class T> QPX_DEV void elastic_recips(bool f, int i, T zu, T su, T zt, T st, T rho, T* vRZ, T* vRS, T* vRZT, T* vRST, T* vD)
+{
+    const T rzu = rcp_(zu), rsu = rcp_(su);
+    vRZ[i] = rzu;
+    vRS[i] = rsu;
+    if (f) {
+        const T rzt = rcp_(zt), rst = rcp_(st);
+        vRZT[i] = rzt;
+        vRST[i] = rst;
+        vD[i] = su * rzu + rcp_(rho + zt * rst);
+    } else {
+        vD[i] = su * rzu;
+    }
+}
+// Start point: w = 1 on the live entries, vX = xu = -T^-1 (c - gamma/(rho + 1)), T = R + diag(1 + 1/(rho + 1));
+// xt = (gamma - xu)/(rho + 1); they are the reference's z_i = -s_i of the augmented QP, shifted as there by the minima over all
+// live entries.  vQT takes t = (zu' + zt' - gamma)/rho for the first pass's residuals.
+template <class T, int NS>
+QPX_DEV void elastic_start_point(const Block& b, int lane, int m, int M8, const T* vX, const T* vGam, const T* vRho, T* vZ, T* vS, T* vZT,
+                                 T* vST, T* vRZ, T* vRS, T* vRZT, T* vRST, T* vD, T* vA, T* vBZ, T* vBS, T* vBZT, T* vBST, T* vQT,
+                                 T* pSigz, T* pSigs)
+{
+    T xu[NS], xt[NS];
+    T mnz = Lim<T>::inf(), mns = Lim<T>::inf();
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        xu[k] = T(0); xt[k] = T(0);
+        if (i < m) {
+            const T rho = vRho[i];
+            xu[k] = vX[i];
+            if (elastic_(rho)) {
+                xt[k] = (vGam[i] - xu[k]) / (rho + T(1));
+                mnz = min2_(mnz, xt[k]);
+                mns = min2_(mns, -xt[k]);
+            }
+            mnz = min2_(mnz, xu[k]);
+            mns = min2_(mns, -xu[k]);
+        }
+    }
+    mnz = wave_min(b, mnz);
+    mns = wave_min(b, mns);
+    const T sigz = (mnz < T(0)) ? (T(1) - mnz) : T(0);
+    const T sigs = (mns < T(0)) ? (T(1) - mns) : T(0);
+    if (lane == 0) { *pSigz = sigz; *pSigs = sigs; }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const T rho = vRho[i];
+            const bool f = elastic_(rho);
+            const T zu = xu[k] + sigz, su = -xu[k] + sigs;
+            const T zt = f ? xt[k] + sigz : T(0), st = f ? -xt[k] + sigs : Lim<T>::inf();
+            vZ[i] = zu; vS[i] = su; vZT[i] = zt; vST[i] = st;
+            vBZ[i] = zu; vBS[i] = su; vBZT[i] = zt; vBST[i] = st;
+            vA[i] = xu[k];
+            vQT[i] = f ? (xu[k] + xt[k] - vGam[i]) / rho : T(0);
+            elastic_recips(f, i, zu, su, zt, st, rho, vRZ, vRS, vRZT, vRST, vD);
+        } else if (i < M8) {
+            vA[i] = T(0);
+        }
+    }
+}
+// Affine step lengths, centring sigma, the corrector's right-hand side.  vX = dzu of the affine solve; vQT takes t's side's
+// corrector rs
+template <class T, int NS>
+QPX_DEV void elastic_affine_step(const Block& b, int lane, int m, T mu, T szdot, const T* vGam, const T* vRho, const T* vZ, const T* vS,
+                                 const T* vZT, const T* vST, const T* vRZ, const T* vRS, const T* vRZT, const T* vRST, const T* vX,
+                                 T* vRH, T* vQT, T* vRSC, T* vDZA, T* vDSA, T* vDZAT, T* vDSAT)
+{
+    T dzu[NS], dsu[NS], dzt[NS], dst[NS], ee[NS];
+    T t = T(0);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        dzu[k] = T(0); dsu[k] = T(0); dzt[k] = T(0); dst[k] = T(0); ee[k] = T(0);
+        if (i < m) {
+            const T rho = vRho[i], x = vX[i], su = vS[i];
+            dzu[k] = x;
+            dsu[k] = -su - x * (su * vRZ[i]);
+            if (elastic_(rho)) {
+                const T zt = vZT[i], wt = zt * vRST[i];
+                const T e = rcp_(rho + wt), g = (vZ[i] + zt - vGam[i]) + x;
+                ee[k] = e;
+                dzt[k] = -wt * g * e;
+                dst[k] = -vST[i] + g * e;
+            }
+            if (dzu[k] < T(0)) t = max2_(t, -dzu[k] * vRZ[i]);
+            if (dsu[k] < T(0)) t = max2_(t, -dsu[k] * vRS[i]);
+            if (dzt[k] < T(0)) t = max2_(t, -dzt[k] * vRZT[i]);
+            if (dst[k] < T(0)) t = max2_(t, -dst[k] * vRST[i]);
+        }
+    }
+    t = wave_max(b, t);
+    T al = (t > T(0)) ? T(1) / t : T(1);
+    al = (al < T(1)) ? al : T(1);
+    T t3 = 0;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            t3 = fma_(vS[i] + al * dsu[k], vZ[i] + al * dzu[k], t3);
+            if (elastic_(vRho[i])) t3 = fma_(vST[i] + al * dst[k], vZT[i] + al * dzt[k], t3);
+        }
+    }
+    t3 = wave_sum(b, t3);
+    T sig = t3 / szdot;
+    sig = sig * sig * sig;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const bool f = elastic_(vRho[i]);
+            const T rsu = (-mu * sig + dsu[k] * dzu[k]) * vRS[i];
+            const T rst = f ? (-mu * sig + dst[k] * dzt[k]) * vRST[i] : T(0);
+            vRSC[i] = rsu;
+            vQT[i] = rst;
+            vRH[i] = rsu * (vS[i] * vRZ[i]) - (f ? rst * ee[k] : T(0));
+            vDZA[i] = dzu[k]; vDSA[i] = dsu[k];
+            vDZAT[i] = dzt[k]; vDSAT[i] = dst[k];
+        }
+    }
+}
+// The combined step with the 0.999 damping, tau, zu' = zu - tau sigma_z, t of the new iterate (vQT), and the next pass's
+// reciprocals and diagonal
+template <class T, int NS>
+QPX_DEV void elastic_final_step(const Block& b, int lane, int m, const T* vGam, const T* vRho, T* vZ, T* vS, T* vZT, T* vST, T* vRZ,
+                                T* vRS, T* vRZT, T* vRST, T* vD, const T* vX, const T* vRSC, T* vQT, const T* vDZA, const T* vDSA,
+                                const T* vDZAT, const T* vDSAT, T* vA, T* pTau, T* pAlphaPrev, T sigz)
+{
+    T dzu[NS], dsu[NS], dzt[NS], dst[NS];
+    T t = T(0);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        dzu[k] = T(0); dsu[k] = T(0); dzt[k] = T(0); dst[k] = T(0);
+        if (i < m) {
+            const T rho = vRho[i], x = vX[i];
+            dzu[k] = vDZA[i] + x;
+            dsu[k] = vDSA[i] + (-vRSC[i] - x) * (vS[i] * vRZ[i]);
+            if (elastic_(rho)) {
+                const T wt = vZT[i] * vRST[i], rst = vQT[i];
+                const T e = rcp_(rho + wt);
+                dzt[k] = vDZAT[i] - (rho * rst + wt * x) * e;
+                dst[k] = vDSAT[i] - (rst - x) * e;
+            }
+            if (dzu[k] < T(0)) t = max2_(t, -dzu[k] * vRZ[i]);
+            if (dsu[k] < T(0)) t = max2_(t, -dsu[k] * vRS[i]);
+            if (dzt[k] < T(0)) t = max2_(t, -dzt[k] * vRZT[i]);
+            if (dst[k] < T(0)) t = max2_(t, -dst[k] * vRST[i]);
+        }
+    }
+    t = wave_max(b, t);
+    T al = (t > T(0)) ? T(1) / t : T(1);
+    al = T(0.999) * al;
+    al = (al < T(1)) ? al : T(1);
+    const T tau = (T(1) - al) * *pTau;
+    const T tsz = tau * sigz;
+    b.wave_sync();           // every lane has read the old tau
+    if (lane == 0) { *pTau = tau; *pAlphaPrev = al; }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const T rho = vRho[i];
+            const bool f = elastic_(rho);
+            const T zu = fma_(al, dzu[k], vZ[i]), su = fma_(al, dsu[k], vS[i]);
+            vZ[i] = zu; vS[i] = su;
+            T zt = T(0), st = Lim<T>::inf(), tv = T(0);
+            if (f) {
+                zt = fma_(al, dzt[k], vZT[i]);
+                st = fma_(al, dst[k], vST[i]);
+                vZT[i] = zt; vST[i] = st;
+                tv = ((zu - tsz) + (zt - tsz) - vGam[i]) / rho;
+            }
+            vQT[i] = tv;
+            vA[i] = zu - tsz;
+            elastic_recips(f, i, zu, su, zt, st, rho, vRZ, vRS, vRZT, vRST, vD);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // The PDIPM loop on the format-3 blob.  Mathematics and control flow: see ipm_body (same
 // reference citations); the factorisation is ldl_inv and every solve is two triangular mat-vecs.
-// kRange: the form's range role (qpx_forms.h: kIpmRangeRole) -- two-sided rows, the range_* blocks above; the one-sided forms
-// compile none of it.
-template <class T, class Mat, int NS, bool kRange, class P>
+// kRole 1, kRange: the form's range role (qpx_forms.h: kIpmRangeRole) -- two-sided rows, the range_* blocks above; kRole 2,
+// kElastic: its elastic role (kIpmElasticRole) -- the elastic_* blocks.  The one-sided forms compile none of either, and a
+// role none of the other.
+template <class T, class Mat, int NS, int kRole, class P>
 QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, const P& g)
 {
+    constexpr bool kRange = kRole == 1, kElastic = kRole == 2;
     constexpr int M8 = Mat::MP, NT = Mat::NT;
     const int n = a.n, m = a.m, q = a.q;
     const FacLayout lay = fac_layout(n, m, q, a.images);
@@ -1167,7 +1366,13 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     T* vDSAL = vDZAL + v;
     T* vQUL = vDSAL + v;
     T* vH = vQUL + v;
-    T* sc = kRange ? vH + v : vX0 + v;              // 16 scalars of the IPM state
+    // elastic role: t's side -- z, s, their reciprocals, best iterate and affine step in the range role's places; vQT (in
+    // vQUL's) is t from the block that forms an iterate to the next pass's residuals and t's side's corrector rs from the affine
+    // step to the combined one; vGam, vRho are gamma and rho (+inf: a hard row) -- one vector more than the range role
+    T *vZT = vZL, *vST = vSL, *vRZT = vRZL, *vRST = vRSL, *vBZT = vBZL, *vBST = vBSL, *vDZAT = vDZAL, *vDSAT = vDSAL, *vQT = vQUL;
+    T* vGam = vH;
+    T* vRho = vGam + v;
+    T* sc = kElastic ? vRho + v : (kRange ? vH + v : vX0 + v);              // 16 scalars of the IPM state
     int* ctrl = reinterpret_cast<int*>(sc + 16);    // 8 elements of control words
     T* scr = sc + 24;     // Mat::scratch_elems()
 
@@ -1186,16 +1391,24 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             if (!(lwg[i] < hg[i])) bad_lower = true;
         bad_lower = b.any(bad_lower);
     }
+    // elastic role: a gamma that is NaN or negative, a rho that is NaN or not positive -- decided in the same way
+    const In<T> gmg(kElastic ? a.gamma : nullptr, (size_t)qp * a.sgamma, io32), rhg(kElastic ? a.rho : nullptr, (size_t)qp * a.srho, io32);
+    if constexpr (kElastic) {
+        for (int i = b.lane(); i < m; i += kWave)
+            if (!(gmg[i] >= T(0)) || !(rhg[i] > T(0))) bad_lower = true;
+        bad_lower = b.any(bad_lower);
+    }
     if ((a.status[qp] & (QPX_ST_Q_NOT_SPD | QPX_ST_A_RANK)) || bad_lower) {
         const T nanv = Lim<T>::inf() - Lim<T>::inf();
         for (int i = b.tid; i < n; i += b.nt) put_(a.zhat, io32, (size_t)qp * n + i, nanv);
         for (int i = b.tid; i < m; i += b.nt) {
             put_(a.lam, io32, (size_t)qp * m + i, nanv);
             put_(a.slack, io32, (size_t)qp * m + i, nanv);
-            if constexpr (kRange) {
+            if constexpr (kRange || kElastic) {
                 put_(a.lam_lo, io32, (size_t)qp * m + i, nanv);
                 put_(a.slack_lo, io32, (size_t)qp * m + i, nanv);
             }
+            if constexpr (kElastic) put_(a.tviol, io32, (size_t)qp * m + i, nanv);
         }
         for (int i = b.tid; i < q; i += b.nt) put_(a.nu, io32, (size_t)qp * q + i, nanv);
         if (b.tid == 0) {
@@ -1251,7 +1464,8 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         sc[kFeasPrev] = T(0); sc[kAlphaPrev] = T(0);
         // || G^T 1 ||: read from the blob once, not once per iteration (a global load on the chain).  Range role: || G^T e ||,
         // e = 1 on the one-sided rows, from the caller -- the blob's scalar is that number only when no row is two-sided
-        if constexpr (kRange) sc[kGt1] = a.gt1 ? In<T>(a.gt1, (size_t)qp, io32)[0] : T(0);
+        // (elastic role: || G'^T 1 || of the augmented QP, from the caller as well)
+        if constexpr (kRange || kElastic) sc[kGt1] = a.gt1 ? In<T>(a.gt1, (size_t)qp, io32)[0] : T(0);
         else sc[kGt1] = F[lay.scal];
         ctrl[kStop] = 0; ctrl[kNnot] = 0; ctrl[kFloor] = 0; ctrl[kSt] = 0; ctrl[kIters] = 0;
     }
@@ -1277,6 +1491,24 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             vZL[i] = T(1); vSL[i] = T(1); vRZL[i] = T(1); vRSL[i] = T(1);
             vDZAL[i] = T(0); vDSAL[i] = T(0); vQUL[i] = T(0);
         }
+        if constexpr (kElastic) {
+            // the start point's system: T = R + diag(1 + 1/(rho + 1)), right-hand side c - gamma/(rho + 1) in vRH (as the range
+            // role's); vA stays 1 for R 1.  A row is elastic where gamma and rho are both finite -- vRho = +inf marks the others
+            T gm = T(0), rho = Lim<T>::inf(), rh = T(0), dd = T(1);
+            if (i < m) {
+                const T g0 = gmg[i], r0 = rhg[i];
+                rh = vC[i];
+                if (g0 < Lim<T>::inf() && r0 < Lim<T>::inf()) {
+                    const T e = rcp_(r0 + T(1));
+                    gm = g0; rho = r0;
+                    rh -= g0 * e;
+                    dd = T(1) + e;
+                }
+            }
+            vGam[i] = gm; vRho[i] = rho; vRH[i] = rh; vD[i] = dd;
+            vZT[i] = T(1); vST[i] = T(1); vRZT[i] = T(1); vRST[i] = T(1);
+            vDZAT[i] = T(0); vDSAT[i] = T(0); vQT[i] = T(0);
+        }
     }
     if constexpr (kRange) {
         if (w0) {            // m' = m + the two-sided rows: the live rows of the doubled QP
@@ -1286,11 +1518,19 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             if (lane == 0) sc[kMp] = mT + cnt;
         }
     }
+    if constexpr (kElastic) {
+        if (w0) {            // m' = m + the elastic rows: the rows of the augmented QP
+            T cnt = T(0);
+            for (int i = lane; i < m; i += kWave) cnt += (gmg[i] < Lim<T>::inf() && rhg[i] < Lim<T>::inf()) ? T(1) : T(0);
+            cnt = wave_sum(b, cnt);
+            if (lane == 0) sc[kMp] = mT + cnt;
+        }
+    }
     // ---- the warm entry: z = max(lam0, f), s = max(s0, f), z' = z (sigma_z = sigma_s = 0, tau = 1 as set above): x = x0 - M^T z
     // and nu = nu0 - W^T z are dual- and equality-feasible by construction, so pass -1 (the start point: one factorisation and
     // one solve) is not needed and the passes begin at 0.  R 1 is formed in pass -1 only: zeroed, tau sigma_z R 1 must not
     // meet what LDS held.  The best iterate is taken at pass 0 as ever; it is set here for a breakdown inside that pass.
-    const bool warm = a.lam0 && ctrl[kWarm];
+    const bool warm = !kElastic && a.lam0 && ctrl[kWarm];
     if (warm) {
         const T fl = a.warm_floor;
         for (int i = b.tid; i < M8; i += NT) {
@@ -1308,7 +1548,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     if (b.tid == 0 && a.warm_used) a.warm_used[qp] = warm;
     const int it0 = warm ? 0 : -1;
     Mat::sync(b);
-    if constexpr (kRange) mT = sc[kMp];
+    if constexpr (kRange || kElastic) mT = sc[kMp];
 
     // ---- pass -1 is the start point: T = R + I, z_i = -T^-1 c, s_i = -z_i, shifts (batch.py:61-87),
     // and R 1 on the way; passes 0.. are the IPM iterations.  One loop so that the factorisation and
@@ -1342,6 +1582,8 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                         szdot = fma_(sk, zk, szdot);
                         if constexpr (kRange) {      // (the reciprocals and the diagonal were formed with the iterate: range_recips)
                             if (two_sided_(vH[i])) szdot = fma_(vSL[i], vZL[i], szdot);
+                        } else if constexpr (kElastic) {      // (... elastic_recips)
+                            if (elastic_(vRho[i])) szdot = fma_(vST[i], vZT[i], szdot);
                         } else {
                             const T rzk = rcp_(zk);
                             vRZ[i] = rzk;
@@ -1357,7 +1599,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             Mat::ahead_pivot0(b, g, ah, vD, scr, rd, m);
         }
         QPX_PROF(4)
-        Mat::template ahead_front<kRange>(b, g, E, vA, vZ, kRange ? vD : vS, scr);      // tile waves: partial sums of R z' (first pass: R 1), T = R + diag(s/z), panel 0's old rows
+        Mat::template ahead_front<kRole != 0>(b, g, E, vA, vZ, kRole != 0 ? vD : vS, scr);      // tile waves: partial sums of R z' (first pass: R 1), T = R + diag(s/z), panel 0's old rows
         Mat::sync(b);
         QPX_PROF(3)                  // (profiling build, chain wave: its wait for the tile waves)
         const int rc = Mat::ldl_inv_ahead(b, g, E, scr, rd, m, [&] { Mat::ahead_gather(b, lane, scr, first ? vR1 : vB); }, [&] {
@@ -1368,7 +1610,14 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             for (int k = 0; k < NS; ++k) {
                 const int i = k * kWave + lane;
                 if (i < m) {
-                    const T rz = vS[i] - vC[i] - vB[i];
+                    T rz = vS[i] - vC[i] - vB[i];
+                    if constexpr (kElastic) {            // ru = su - c - R zu' - t, rt = st - t
+                        if (elastic_(vRho[i])) {
+                            const T tv = vQT[i], rt = vST[i] - tv;
+                            rz -= tv;
+                            pri2 = fma_(rt, rt, pri2);
+                        }
+                    }
                     pri2 = fma_(rz, rz, pri2);
                     if constexpr (kRange) {
                         const T hl = vH[i];
@@ -1394,7 +1643,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 bres = resid; nnot = 0;
                 for (int i = lane; i < m; i += kWave) {
                     vBZ[i] = vZ[i]; vBS[i] = vS[i];
-                    if constexpr (kRange) { vBZL[i] = vZL[i]; vBSL[i] = vSL[i]; }
+                    if constexpr (kRange || kElastic) { vBZL[i] = vZL[i]; vBSL[i] = vSL[i]; }
                 }
             } else if (a.stall_policy == 1 || (a.stall_policy == 2 && mT * mu < feas)) {
                 nnot += 1;
@@ -1432,6 +1681,10 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                         const T hl = vH[i];
                         vQUL[i] = qu;
                         vRH[i] = two_sided_(hl) ? ((vZ[i] * vRS[i]) * qu - (vZL[i] * vRSL[i]) * (hl - qu)) * vD[i] : qu;
+                    } else if constexpr (kElastic) {
+                        // (c + R zu) + e (zu + zt - gamma), e = 1/(rho + wt); a hard row keeps qu
+                        const T rho = vRho[i];
+                        vRH[i] = elastic_(rho) ? qu + (vZ[i] + vZT[i] - vGam[i]) * rcp_(rho + vZT[i] * vRST[i]) : qu;
                     } else {
                         vRH[i] = qu;
                     }
@@ -1449,6 +1702,9 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                         if constexpr (kRange) {
                             if (i < m) { const bool f = two_sided_(vH[i]); vBZL[i] = f ? T(1) : T(0); vBSL[i] = f ? T(1) : Lim<T>::inf(); }
                         }
+                        if constexpr (kElastic) {
+                            if (i < m) { const bool f = elastic_(vRho[i]); vBZT[i] = f ? T(1) : T(0); vBST[i] = f ? T(1) : Lim<T>::inf(); }
+                        }
                         vA[i] = T(0);
                     }
                 }
@@ -1456,12 +1712,14 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             break;
         }
         QPX_PROF(1)
-        Mat::template solve_neg<true>(b, g, E, rd, m, (first && !kRange) ? vC : vRH, vX, vTm, scr);
+        Mat::template solve_neg<true>(b, g, E, rd, m, (first && kRole == 0) ? vC : vRH, vX, vTm, scr);
         QPX_PROF(6)
         if (first) {
             if (w0) {
                 if constexpr (kRange) range_start_point<T, NS>(b, lane, m, M8, vX, vRH, vC, vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vA,
                                                                vBZ, vBS, vBZL, vBSL, sc + kSigz, sc + kSigs);
+                else if constexpr (kElastic) elastic_start_point<T, NS>(b, lane, m, M8, vX, vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT, vRST, vD,
+                                                                        vA, vBZ, vBS, vBZT, vBST, vQT, sc + kSigz, sc + kSigs);
                 else ipm_start_point<T, NS>(b, lane, m, M8, vX, vZ, vS, vA, vBZ, vBS, sc + kSigz, sc + kSigs);
             }
             Mat::sync(b);
@@ -1471,6 +1729,8 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         if (w0) {
             if constexpr (kRange) range_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vX,
                                                            vRH, vQUL, vRSC, vDZA, vDSA, vDZAL, vDSAL);
+            else if constexpr (kElastic) elastic_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT,
+                                                                    vRST, vX, vRH, vQT, vRSC, vDZA, vDSA, vDZAT, vDSAT);
             else ipm_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vZ, vS, vRZ, vRS, vD, vX, vRSC, vRH, vDZA, vDSA);
         }
         Mat::sync(b);
@@ -1484,6 +1744,8 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         if (w0) {
             if constexpr (kRange) range_final_step<T, NS>(b, lane, m, vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vX, vRH, vRSC, vQUL, vDZA,
                                                           vDSA, vDZAL, vDSAL, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
+            else if constexpr (kElastic) elastic_final_step<T, NS>(b, lane, m, vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT, vRST, vD, vX, vRSC,
+                                                                   vQT, vDZA, vDSA, vDZAT, vDSAT, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
             else ipm_final_step<T, NS>(b, lane, m, vZ, vS, vRZ, vRS, vD, vX, vRSC, vDZA, vDSA, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
         }
         Mat::sync(b);
@@ -1504,11 +1766,25 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 const int i = k * kWave + lane;
                 if (i < m) {
                     const T zk = vZ[i], sk = vS[i];
-                    const T rz = sk - vC[i] - vB[i];
+                    T rz = sk - vC[i] - vB[i];
+                    if constexpr (kElastic) {            // (as the chain-wave order above)
+                        if (elastic_(vRho[i])) rz -= vQT[i];
+                    }
                     pri2 = fma_(rz, rz, pri2);
                     szdot = fma_(sk, zk, szdot);
                     const T qu = vC[i] + vB[i] + tsz * vR1[i];          // affine right-hand side c + R z
-                    if constexpr (kRange) {
+                    if constexpr (kElastic) {
+                        const T rho = vRho[i];
+                        if (elastic_(rho)) {
+                            const T zt = vZT[i], st = vST[i];
+                            const T rt = st - vQT[i];
+                            pri2 = fma_(rt, rt, pri2);
+                            szdot = fma_(st, zt, szdot);
+                            vRH[i] = qu + (zk + zt - vGam[i]) * rcp_(rho + zt * vRST[i]);
+                        } else {
+                            vRH[i] = qu;
+                        }
+                    } else if constexpr (kRange) {
                         // (as the chain-wave order above: the lower side's residual, and the right-hand side of the m x m system;
                         // the reciprocals and the diagonal were formed with the iterate: range_recips)
                         const T hl = vH[i];
@@ -1549,7 +1825,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 bres = resid; nnot = 0;
                 for (int i = lane; i < m; i += kWave) {
                     vBZ[i] = vZ[i]; vBS[i] = vS[i];
-                    if constexpr (kRange) { vBZL[i] = vZL[i]; vBSL[i] = vSL[i]; }
+                    if constexpr (kRange || kElastic) { vBZL[i] = vZL[i]; vBSL[i] = vSL[i]; }
                 }
             } else if (a.stall_policy == 1 || (a.stall_policy == 2 && mT * mu < feas)) {
                 nnot += 1;
@@ -1592,6 +1868,9 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                         if constexpr (kRange) {
                             if (i < m) { const bool f = two_sided_(vH[i]); vBZL[i] = f ? T(1) : T(0); vBSL[i] = f ? T(1) : Lim<T>::inf(); }
                         }
+                        if constexpr (kElastic) {
+                            if (i < m) { const bool f = elastic_(vRho[i]); vBZT[i] = f ? T(1) : T(0); vBST[i] = f ? T(1) : Lim<T>::inf(); }
+                        }
                         vA[i] = T(0);
                     }
                 }
@@ -1600,12 +1879,14 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         }
         // first pass: z_i = -T^-1 c; iterations: affine scaling direction dz_aff = -T^-1 (c + R z)
         QPX_PROF(1)
-        Mat::template solve_neg<true>(b, g, E, rd, m, (first && !kRange) ? vC : vRH, vX, vTm, scr);
+        Mat::template solve_neg<true>(b, g, E, rd, m, (first && kRole == 0) ? vC : vRH, vX, vTm, scr);
         QPX_PROF(6)
         if (first) {
             if (w0) {
                 if constexpr (kRange) range_start_point<T, NS>(b, lane, m, M8, vX, vRH, vC, vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vA,
                                                                vBZ, vBS, vBZL, vBSL, sc + kSigz, sc + kSigs);
+                else if constexpr (kElastic) elastic_start_point<T, NS>(b, lane, m, M8, vX, vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT, vRST, vD,
+                                                                        vA, vBZ, vBS, vBZT, vBST, vQT, sc + kSigz, sc + kSigs);
                 else ipm_start_point<T, NS>(b, lane, m, M8, vX, vZ, vS, vA, vBZ, vBS, sc + kSigz, sc + kSigs);
             }
             Mat::sync(b);
@@ -1615,6 +1896,8 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         if (w0) {
             if constexpr (kRange) range_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vX,
                                                            vRH, vQUL, vRSC, vDZA, vDSA, vDZAL, vDSAL);
+            else if constexpr (kElastic) elastic_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT,
+                                                                    vRST, vX, vRH, vQT, vRSC, vDZA, vDSA, vDZAT, vDSAT);
             else ipm_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vZ, vS, vRZ, vRS, vD, vX, vRSC, vRH, vDZA, vDSA);
         }
         Mat::sync(b);
@@ -1624,6 +1907,8 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         if (w0) {
             if constexpr (kRange) range_final_step<T, NS>(b, lane, m, vH, vZ, vS, vZL, vSL, vRZ, vRS, vRZL, vRSL, vD, vX, vRH, vRSC, vQUL, vDZA,
                                                           vDSA, vDZAL, vDSAL, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
+            else if constexpr (kElastic) elastic_final_step<T, NS>(b, lane, m, vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT, vRST, vD, vX, vRSC,
+                                                                   vQT, vDZA, vDSA, vDZAT, vDSAT, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
             else ipm_final_step<T, NS>(b, lane, m, vZ, vS, vRZ, vRS, vD, vX, vRSC, vDZA, vDSA, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
         }
         Mat::sync(b);
@@ -1648,6 +1933,12 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 put_(a.lam_lo, io32, (size_t)qp * m + i, bzl);
                 put_(a.slack_lo, io32, (size_t)qp * m + i, vBSL[i]);
                 vA[i] = two_sided_(vH[i]) ? bz - bzl : bz - bts;
+            } else if constexpr (kElastic) {
+                const T bzt = vBZT[i], rho = vRho[i];
+                put_(a.lam_lo, io32, (size_t)qp * m + i, bzt);
+                put_(a.slack_lo, io32, (size_t)qp * m + i, vBST[i]);
+                put_(a.tviol, io32, (size_t)qp * m + i, elastic_(rho) ? ((bz - bts) + (bzt - bts) - vGam[i]) / rho : T(0));
+                vA[i] = bz - bts;
             } else {
                 vA[i] = bz - bts;
             }
@@ -1688,19 +1979,21 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
 }
 
 // The loop body runs once per wave role (the tile kernels' chain-wave form: Mat::with_role); every other form has one.
-template <class T, class Mat, int NS, bool kRange = false>
+template <class T, class Mat, int NS, int kRole = 0>
 QPX_DEV void ipm_loop_body(const Block& b, const IpmArgs<T>& a, int qp, T* lds)
 {
     typename Mat::Pos g(b);
     g.assign(b, reinterpret_cast<int*>(lds));      // (an LDS word nothing else uses before the barriers inside)
-    Mat::with_role(g, [&](const auto& gp) { ipm_loop_role<T, Mat, NS, kRange>(b, a, qp, lds, gp); });
+    Mat::with_role(g, [&](const auto& gp) { ipm_loop_role<T, Mat, NS, kRole>(b, a, qp, lds, gp); });
 }
 
-// (NBL >= kIpmRangeRole: the range role of the form with NBL - kIpmRangeRole blocks, qpx_forms.h)
+// (NBL >= kIpmRangeRole: the range role of the form with NBL - kIpmRangeRole blocks, >= kIpmElasticRole: its elastic role,
+// qpx_forms.h)
 template <class T, int GS, int NBL, int NS>
 QPX_DEV void ipm_grid_body(const Block& b, const IpmArgs<T>& a, int qp, T* lds)
 {
-    if constexpr (NBL >= kIpmRangeRole) ipm_loop_body<T, GridMat<T, GS, NBL - kIpmRangeRole>, NS, true>(b, a, qp, lds);
+    if constexpr (NBL >= kIpmElasticRole) ipm_loop_body<T, GridMat<T, GS, NBL - kIpmElasticRole>, NS, 2>(b, a, qp, lds);
+    else if constexpr (NBL >= kIpmRangeRole) ipm_loop_body<T, GridMat<T, GS, NBL - kIpmRangeRole>, NS, 1>(b, a, qp, lds);
     else ipm_loop_body<T, GridMat<T, GS, NBL>, NS>(b, a, qp, lds);
 }
 

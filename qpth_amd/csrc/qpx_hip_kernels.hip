@@ -90,6 +90,9 @@ QPX_FORMS_IPM_GRID(QPX_INST)
 // (NBL + kIpmRangeRole: the form's range role, qpx_ipm_range -- float64 arithmetic only)
 #define QPX_INSTR(NBL, NS) template int launch_ipm_grid<double, NBL + kIpmRangeRole, NS>(const IpmArgs<double>&, size_t, void*);
 QPX_FORMS_IPM_RANGE_GRID(QPX_INSTR)
+// (NBL + kIpmElasticRole: its elastic role, qpx_ipm_elastic)
+#define QPX_INSTE(NBL, NS) template int launch_ipm_grid<double, NBL + kIpmElasticRole, NS>(const IpmArgs<double>&, size_t, void*);
+QPX_FORMS_IPM_RANGE_GRID(QPX_INSTE)
 #endif
 #elif QPX_TU_KERNEL == 7
 // (NBL >= kKktMultiRole: the form's multi-right-hand-side role, >= kKktB2Role: its second-order role, qpx_forms.h)
@@ -241,6 +244,8 @@ QPX_INSTT(7, QPX_TILE_ONLY, 2, QPX_TILE_ONLY == 4)
 QPX_FORMS_IPM_TILE(QPX_INSTT)
 #define QPX_INSTTR(NBL, NW, NS, CH) template int launch_ipm_tile<NBL + kIpmRangeRole, NW, NS, CH>(const IpmArgs<double>&, size_t, void*);
 QPX_FORMS_IPM_RANGE_TILE(QPX_INSTTR)
+#define QPX_INSTTE(NBL, NW, NS, CH) template int launch_ipm_tile<NBL + kIpmElasticRole, NW, NS, CH>(const IpmArgs<double>&, size_t, void*);
+QPX_FORMS_IPM_RANGE_TILE(QPX_INSTTE)
 #endif
 #endif
 

@@ -177,6 +177,12 @@ template <class T> struct IpmArgs {
     long long slo = 0;
     const T* gt1 = nullptr;
     T *lam_lo = nullptr, *slack_lo = nullptr;
+    // elastic rows (qpx_ipm_elastic; the forms of kIpmElasticRole only): gamma, rho (B,m), batch strides sgamma, srho (0 = shared),
+    // +inf in either = a hard row; gt1 above (B) = sqrt(|| G^T 1 ||^2 + 4 k), k elastic rows; lam_lo, slack_lo above: the
+    // multipliers and slacks of t >= 0 (0 and +inf on a hard row); tviol (B,m): t
+    const T *gamma = nullptr, *rho = nullptr;
+    long long sgamma = 0, srho = 0;
+    T* tviol = nullptr;
 };
 
 template <class T> struct KktArgs {

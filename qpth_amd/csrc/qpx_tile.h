@@ -1313,9 +1313,9 @@ template <int NBL, int NW, bool CH = false> struct TileMat {
     }
 };
 
-QPX_LAYOUT_HD size_t lds_elems_ipm_tile(int nbl, int nw, int n, int q, bool chain = false, bool range = false)
+QPX_LAYOUT_HD size_t lds_elems_ipm_tile(int nbl, int nw, int n, int q, bool chain = false, int role = 0)
 {
-    return lds_elems_ipm_loop(16 * (size_t)nbl, tile_scratch_elems(nbl, chain ? nw - 1 : nw, chain), n, q, range);
+    return lds_elems_ipm_loop(16 * (size_t)nbl, tile_scratch_elems(nbl, chain ? nw - 1 : nw, chain), n, q, role);
 }
 
 QPX_LAYOUT_HD size_t lds_elems_kkt_tile(int nbl, int nw, int n, int q, bool chain = false)
@@ -1357,8 +1357,10 @@ QPX_LAYOUT_HD size_t lds_elems_centre_tile(int nbl, int n, int q, bool chain)
 template <int NBL, int NW, int NS, bool CH = false>
 QPX_DEV void ipm_tile_body(const Block& b, const IpmArgs<double>& a, int qp, double* lds)
 {
-    // (NBL >= kIpmRangeRole: the range role of the form with NBL - kIpmRangeRole tile rows, qpx_forms.h)
-    if constexpr (NBL >= kIpmRangeRole) ipm_loop_body<double, TileMat<NBL - kIpmRangeRole, NW, CH>, NS, true>(b, a, qp, lds);
+    // (NBL >= kIpmRangeRole: the range role of the form with NBL - kIpmRangeRole tile rows, >= kIpmElasticRole: its elastic role,
+    // qpx_forms.h)
+    if constexpr (NBL >= kIpmElasticRole) ipm_loop_body<double, TileMat<NBL - kIpmElasticRole, NW, CH>, NS, 2>(b, a, qp, lds);
+    else if constexpr (NBL >= kIpmRangeRole) ipm_loop_body<double, TileMat<NBL - kIpmRangeRole, NW, CH>, NS, 1>(b, a, qp, lds);
     else ipm_loop_body<double, TileMat<NBL, NW, CH>, NS>(b, a, qp, lds);
 }
 

@@ -35,7 +35,8 @@ def default_stall_policy(B):
 class IpmResult:
     __slots__ = ("zhat", "nu", "lam", "slacks", "iters", "status", "best_resid", "trace", "_warm_used",
                  "centre_resid", "centre_steps",         # these two: set by KKTFactors.centre only
-                 "lam_lo", "slacks_lo")                  # ... and these by KKTFactors.ipm_range only
+                 "lam_lo", "slacks_lo",                  # ... these by KKTFactors.ipm_range only
+                 "lam_t", "slacks_t", "t")               # ... and these by KKTFactors.ipm_elastic only
 
     @property
     def warm_used(self):
@@ -132,6 +133,19 @@ def as_lower(lower, Q, nineq, nBatch=1):
     if lower.dim() not in (1, 2) or lower.size(-1) != nineq or (lower.dim() == 2 and nBatch > 1 and lower.size(0) != nBatch):
         raise ValueError("qpth_amd: lower has shape %s; expected (nBatch, %d) or (%d,)" % (tuple(lower.shape), nineq, nineq))
     return lower
+
+
+def as_l1(l1, Q, nineq, nBatch=1):
+    """The linear penalties of elastic rows as every entry point takes them, as as_rho: a tensor of Q's dtype and
+    device, shape (nBatch, nineq), (nineq,) or (), or a Python number (-> a 0-dim tensor).  Raises ValueError otherwise; the
+    VALUES (>= 0, +inf = a hard row) are checked by the loop kernel."""
+    if not torch.is_tensor(l1):
+        l1 = torch.tensor(float(l1), dtype=Q.dtype, device=Q.device)
+    if l1.dtype != Q.dtype or l1.device != Q.device:
+        raise ValueError("qpth_amd: l1 is %s on %s, the QP is %s on %s" % (l1.dtype, l1.device, Q.dtype, Q.device))
+    if l1.dim() > 2 or (l1.dim() >= 1 and l1.size(-1) != nineq) or (l1.dim() == 2 and nBatch > 1 and l1.size(0) != nBatch):
+        raise ValueError("qpth_amd: l1 has shape %s; expected (nBatch, %d), (%d,) or ()" % (tuple(l1.shape), nineq, nineq))
+    return l1
 
 
 class _PinnedPool:
@@ -321,13 +335,16 @@ class KKTFactors:
             # two-sided rows: the words ipm_range copied in FRONT of its loop launch -- the pre-factorisation's status and, per
             # QP, whether a lower entry is NaN, +inf or not below its h (the loop's own test, formed by torch operations): they
             # stand in for the read-back of the pre-factorisation's words, and the host still never waits for the loop
-            host, ev = rng
+            host, ev = rng[:2]
             if ev is not None:
                 ev.synchronize()
             words = host.cpu().numpy()
             self._pre_bits = int(np.bitwise_or.reduce(words[0]))      # (a later call reads these, not the pinned buffer)
             st = self._pre_bits & mask
-            bad_lower = bool(words[1].any())
+            # (elastic rows, ipm_elastic: a word per QP for a bad gamma and one for a bad rho instead, with their messages)
+            for row, msg in zip(words[1:], rng[2] if len(rng) > 2 else ("lower must be below h",)):
+                if row.any():
+                    bad_lower = bad_lower or msg
             if self._pre_host is not None:
                 self._release_pinned(False)
         elif self._pre_soft is not None:
@@ -354,7 +371,7 @@ a non-zero diagonal.
         if st & _lib.ST_NONFINITE:
             raise ValueError("rho must be positive")
         if bad_lower:
-            raise ValueError("lower must be below h")
+            raise ValueError(bad_lower)
 
     def _no_refine_on_soft(self, refine, what):
         """refinement evaluates residuals from the caller's Q, G, A: of the HARD QP"""
@@ -577,6 +594,96 @@ a non-zero diagonal.
                 dlo = -dz * share
                 dlo = dlo.mean(0) if sl else dlo
         return dQ, dp, dG, dh, dA, db, dlo
+
+    # -- elastic rows G z <= h + t, t >= 0, penalty gamma't + 1/2 t'diag(rho)t -----------
+    def elastic_ok(self):
+        """does qpx_ipm_elastic serve these factors (under the knob they were built with)?  float64 tensors, the thread-grid /
+        tile kernels' sizes (nz+neq+nineq <= 208), HARD factors (rho enters the loop, not the pre-factorisation)"""
+        if self.soft or self.wide or self.dtype != torch.float64 or not hasattr(self.lib.dll, "qpx_elastic_supported"):
+            return False
+        with self._knob():
+            return bool(self.lib.dll.qpx_elastic_supported(_lib.QPX_F64, self.n, self.m, self.q))
+
+    def _elastic_refusal(self):
+        return ValueError("qpth_amd: elastic rows (l1) are served for float64 tensors up to nz + neq + nineq = 208 under the "
+                          "default knob, on hard factors; got %s, nz = %d, nineq = %d, neq = %d%s.  Write the augmented dense QP "
+                          "in (z, t) instead" % (str(self.dtype).replace("torch.", ""), self.n, self.m, self.q,
+                                                 ", soft rows" if self.soft else ""))
+
+    def gt1_elastic(self, gamma, rho):
+        """sqrt(|| G^T 1 ||^2 + 4 k) per QP, k its elastic rows (gamma and rho finite, the kernel's test): the augmented QP's
+        || G'^T 1 || of the stop rule.  torch operations, no host sync (gt1_of is the model)."""
+        G = self.G
+        if G.dim() == 3 and (G.size(0) == 1 or G.stride(0) == 0):
+            G = G[0]
+        g2 = G.sum(-2).square().sum(-1)
+        k = (torch.isfinite(gamma) & torch.isfinite(rho)).to(self.dtype).sum(-1)
+        return torch.sqrt(g2 + 4.0 * k).reshape(-1).expand(self.B).contiguous()
+
+    def ipm_elastic(self, p, h, gamma, rho, b, eps=1e-12, maxIter=20, notImprovedLim=3, stall_policy=None, want_trace=False):
+        """The IPM loop for  G z <= h + t, t >= 0  with the penalty  gamma't + 1/2 t'diag(rho)t  in nineq rows (qpx_ipm_elastic):
+        the iterates of ipm() on the augmented QP in (z, t), one launch, no host sync.  gamma, rho (B, nineq), (1, nineq) or
+        (nineq,); +inf in either = a hard row.  The result has lam, slacks (= h + t - G zhat) of the rows and lam_t, slacks_t, t
+        of t >= 0 (0, +inf and 0 on a hard row).  A gamma entry that is NaN or negative, a rho entry that is NaN or not
+        positive: QPX_ST_NONFINITE in `status` (raise_on_failure)."""
+        if not self.elastic_ok():
+            raise self._elastic_refusal()
+        B, n, m, q = self.B, self.n, self.m, self.q
+        dt, dev = self.dtype, self.device
+        self._check(p, n, "p")
+        self._check(h, m, "h")
+        self._check(gamma, m, "l1")
+        self._check(rho, m, "rho")
+        if q:
+            if b is None or b.nelement() == 0:
+                raise RuntimeError("qpth_amd: A has %d rows but b is empty" % q)
+            self._check(b, q, "b")
+        r = IpmResult()
+        r.zhat = torch.empty(B, n, dtype=dt, device=dev)
+        r.nu = torch.empty(B, q, dtype=dt, device=dev)
+        r.lam = torch.empty(B, m, dtype=dt, device=dev)
+        r.slacks = torch.empty(B, m, dtype=dt, device=dev)
+        r.lam_t = torch.empty(B, m, dtype=dt, device=dev)
+        r.slacks_t = torch.empty(B, m, dtype=dt, device=dev)
+        r.t = torch.empty(B, m, dtype=dt, device=dev)
+        r.iters = torch.empty(B, dtype=torch.int32, device=dev)
+        r.best_resid = torch.empty(B, dtype=dt, device=dev)
+        r.trace = torch.full((maxIter, B, 3), float('nan'), dtype=dt, device=dev) if want_trace else None
+        # the status words of THIS launch, and what raise_on_failure reads, copied to pinned memory in front of the loop
+        # launch: as ipm_range does
+        r.status = self.status.clone()
+        r._warm_used = None
+        gamma, rho = gamma.detach(), rho.detach()
+        bad_g = (~(gamma >= 0)).any(-1).expand(B).to(torch.int32)
+        bad_r = (~(rho > 0)).any(-1).expand(B).to(torch.int32)
+        words = torch.stack((self.status, bad_g, bad_r))
+        msgs = ("l1 must be non-negative", "rho must be positive")
+        if words.is_cuda and not torch.cuda.is_current_stream_capturing():
+            host = torch.empty(words.shape, dtype=torch.int32, pin_memory=True)
+            host.copy_(words, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            self._range = (host, ev, msgs)
+        else:
+            self._range = (words, None, msgs)
+        if stall_policy is None:
+            stall_policy = default_stall_policy(B)
+        gt1 = self.gt1_elastic(gamma, rho)
+        with self._knob():
+            self.lib.ipm_elastic(B, n, m, q, p, h, gamma, rho, gt1, b if q else None, self.blob, self.sfac, eps, maxIter,
+                                 notImprovedLim, stall_policy, r.zhat, r.nu if q else None, r.lam, r.slacks, r.lam_t,
+                                 r.slacks_t, r.t, r.iters, r.status, r.best_resid, r.trace)
+        return r
+
+    @staticmethod
+    def elastic_eff(lam, slacks, lam_t, slacks_t, rho):
+        """(slack_eff, dt) of an elastic solution: the derivative entry points serve it on the hard factors given lam and
+        slack_eff = clamp(lam) (1/du + 1/(rho + dt)), du = clamp(lam)/clamp(slacks), dt = clamp(lam_t)/clamp(slacks_t) (clamps at
+        1e-8, qp.py:148) -- their d = clamp(lam)/clamp(slack_eff) is then the augmented QP's 1/(1/du + 1/(rho + dt)).  On a hard
+        row (rho = +inf) slack_eff is clamp(slacks).  It is >= clamp(slacks), so the kernels' own clamp leaves it alone."""
+        lc, sc = lam.clamp(min=1e-8), slacks.clamp(min=1e-8)
+        dt = lam_t.clamp(min=1e-8) / slacks_t.clamp(min=1e-8)
+        return sc + lc / (rho + dt), dt
 
     # -- factor_kkt + solve_kkt (batch.py:435-470, 349-372) ----------------------------------
     def solve_kkt(self, d, rx, rs, rz, ry, refine=0):

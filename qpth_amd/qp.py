@@ -19,6 +19,9 @@ QPFunction(...)(Q, p, G, h, A, b, kappa=kappa) returns the point of the CENTRAL 
 log-barrier smoothing of the QP, C-infinity in all parameters and in kappa; one more launch in the forward (qpx_centre).
 QPFunction(...)(Q, p, G, h, A, b, lower=l) solves  l <= Gz <= h  in nineq rows -- not [G; -G] z <= [h; -l] in 2 nineq --, differentiable
 in l as well: the loop's and the backward's range role, the same number of launches (qpx_ipm_range).
+QPFunction(...)(Q, p, G, h, A, b, rho, l1=gamma) makes the rows ELASTIC: the exact penalty gamma't + 1/2 t'diag(rho)t on the violations
+t >= 0 of Gz <= h + t, in nineq rows and nz variables -- not the augmented dense QP in (z, t) --, differentiable in gamma and rho:
+the loop's elastic role on the hard QP's factors, the backward as it stands (qpx_ipm_elastic).
 """
 from enum import Enum
 
@@ -27,7 +30,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .kkt import KKTFactors, as_kappa, as_lower, as_rho
+from .kkt import KKTFactors, as_kappa, as_l1, as_lower, as_rho
 from .solvers.pdipm import batch as pdipm_b
 from .util import expandParam, extract_nBatch
 
@@ -61,8 +64,27 @@ def f64_arithmetic_serves(nz, nineq, neq, lib=None):
 def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                maxIter=20, solver=QPSolvers.PDIPM_BATCHED,
                check_Q_spd=True, refine=None, duals=False, warm_start=None, kappa_tol=1e-9, kappa_steps=20):
-    """Returns f(Q, p, G, h, A, b, rho=None, kappa=None, lower=None).  `refine`, `duals`, `warm_start` and the inputs `rho`, `kappa`
-    and `lower` are what the reference does not have.
+    """Returns f(Q, p, G, h, A, b, rho=None, kappa=None, lower=None, l1=None).  `refine`, `duals`, `warm_start` and the inputs `rho`,
+    `kappa`, `lower` and `l1` are what the reference does not have.
+    l1: elastic inequality rows, together with rho,
+          min 1/2 z'Qz + p'z + sum_i ( l1_i t_i + 1/2 rho_i t_i^2 )   s.t.  Gz <= h + t,  t >= 0,  Az = b,
+      the EXACT penalty with a quadratic tail: where the hard QP is feasible and l1_i exceeds its multipliers the solution is the
+      hard QP's with t = 0 exactly; elsewhere the QP stays feasible and the multipliers stay bounded (lam_i = l1_i + rho_i t_i on a
+      violated row).  The iterates, iteration counts and solution of the reference on the augmented QP in (z, t) -- nz + nineq
+      variables, 2 nineq rows --, whose Newton system collapses to the nineq x nineq system the loop factors anyway, on the HARD
+      QP's factors.  l1 and rho: tensors of the other inputs' dtype and device, shape (nBatch, nineq), (nineq,) (shared by the
+      batch) or () (one for every row), or Python floats; l1 >= 0, rho > 0, +inf in either = a hard row, so l1 = +inf everywhere
+      is the six-input QP and l1 = 0 the soft rows of rho alone.  An l1 entry that is NaN or negative raises
+      ValueError("l1 must be non-negative"), a rho entry that is NaN or not positive ValueError("rho must be positive"), from the
+      forward.  l1 without rho raises ValueError: rho is the penalty's curvature, and the pure l1 penalty (rho = 0, a singular
+      augmented Q) is not served.  Both are differentiable inputs, the seventh and eighth, in reverse and in forward mode
+      (d loss / d l1 = dz / (dt + rho), d loss / d rho = t d loss / d l1 with dz the inequality block of the backward's KKT
+      solution and dt = lam_t / s_t of the rows t >= 0: exactly 0 on a hard row); a shared one gets the `.mean(0)` convention,
+      a scalar is summed over the rows as well.  duals=True returns (zhat, nu, lam, slacks), slacks = h + t - G zhat, as for the
+      hard QP.  float64 inputs at sizes the thread-grid / tile kernels serve (nz+neq+nineq <= 208) only; not together with
+      kappa, lower, warm_start, refine > 0, float32 inputs or solver=QPSolvers.CVXPY: each a ValueError from the call that names
+      the augmented dense QP as the way out.  Second derivatives are not served: RuntimeError from the second grad.  l1=None is
+      the call as before: the same nodes and launches.
     lower: two-sided inequality rows,
           min 1/2 z'Qz + p'z   s.t.  lower <= Gz <= h,  Az = b,
       box and range constraints in nineq rows: the iterates, iteration counts and solution of the reference on the doubled QP
@@ -454,6 +476,117 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                 grads = grads[:4] + (None, None) + grads[6:]
             return grads
 
+    class QPElasticFunctionFn(Function):
+        """the node of elastic rows: rho and l1, the seventh and eighth differentiable inputs, behind the six parameters (DESIGN
+        4.12).  Forward: the hard QP's factors and the loop's elastic role; the derivatives run on the same factors, in the
+        launches of the hard QP, given lam and the effective slack (KKTFactors.elastic_eff)."""
+        @staticmethod
+        def forward(ctx, Q_, p_, G_, h_, A_, b_, rho_, l1_):
+            nBatch = extract_nBatch(Q_, p_, G_, h_, A_, b_)
+            for X in (rho_, l1_):
+                if X.dim() == 2:
+                    nBatch = max(nBatch, X.size(0))
+            nineq = G_.size(-2)
+            Q, _ = expandParam(Q_, nBatch, 3)
+            p, _ = expandParam(p_, nBatch, 2)
+            G, _ = expandParam(G_, nBatch, 3)
+            h, _ = expandParam(h_, nBatch, 2)
+            A, _ = expandParam(A_, nBatch, 3)
+            b, _ = expandParam(b_, nBatch, 2)
+            ctx.neq = neq = A_.size(-2) if A_.nelement() > 0 else 0
+            gam = l1_.detach().expand(nineq).unsqueeze(0) if l1_.dim() < 2 else l1_.detach()
+            rho = rho_.detach().expand(nineq).unsqueeze(0) if rho_.dim() < 2 else rho_.detach()
+            fac = KKTFactors.build(Q, G, A, nBatch)
+            res = fac.ipm_elastic(p, h, gam, rho, b, eps, maxIter, notImprovedLim, want_trace=(verbose == 1))
+            # one small read-back: the reference raises here too (qp.py:81-85), and so does a bad l1 or rho entry
+            fac.raise_on_failure(check_Q_spd)
+            if verbose == 1:
+                _print_trace(res)
+            if verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
+                print(pdipm_b.INACC_ERR)
+            ctx.fac = fac
+            # a row is hard where either is +inf (the kernel's rule): rho = +inf there for the derivatives' formulas
+            ctx.rho = torch.where(torch.isfinite(gam), rho, torch.full_like(rho, float("inf")))
+            ctx.seff, ctx.dt = fac.elastic_eff(res.lam, res.slacks, res.lam_t, res.slacks_t, ctx.rho)
+            ctx.t = res.t
+            ctx.rho_dim, ctx.l1_dim = rho_.dim(), l1_.dim()
+            ctx.zhat, ctx.nus, ctx.lams = res.zhat.detach(), res.nu.detach(), res.lam.detach()
+            ctx.save_for_backward(Q_, p_, G_, h_, A_, b_, rho_, l1_)
+            if not duals:
+                return res.zhat
+            ctx.set_materialize_grads(False)
+            if neq == 0:
+                ctx.mark_non_differentiable(res.slacks, res.nu)
+            else:
+                ctx.mark_non_differentiable(res.slacks)
+            return res.zhat, res.nu, res.lam, res.slacks
+
+        @staticmethod
+        def jvp(ctx, dQ, dp, dG, dh, dA, db, drho, dl1):
+            # the tangents of l1 and rho act on h: th -= (tl1 + t trho) / (dt + rho) (exactly nothing on a hard row)
+            if drho is not None or dl1 is not None:
+                th = (0 if dl1 is None else dl1) + (0 if drho is None else ctx.t * drho)
+                th = -th / (ctx.dt + ctx.rho)
+                dh = th if dh is None else dh + th
+            if not duals:
+                return ctx.fac.jvp(ctx.zhat, ctx.lams, ctx.seff, ctx.nus, (dQ, dp, dG, dh, dA, db))
+            zt, lt, nt = ctx.fac.jvp(ctx.zhat, ctx.lams, ctx.seff, ctx.nus, (dQ, dp, dG, dh, dA, db), want_duals=True)
+            return zt, nt, lt, None
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
+            Q, p, G, h, A, b = ctx.saved_tensors[:6]
+            neq = ctx.neq
+            if dl_dzhat is None and dl_dlam is None and (dl_dnu is None or neq == 0):
+                return (None,) * 8
+            shared = (Q.dim() == 2, p.dim() == 1, G.dim() == 2, h.dim() == 1, A.dim() == 2, b.dim() == 1)
+            want_pen = ctx.needs_input_grad[6] or ctx.needs_input_grad[7]
+            grads = ctx.fac.backward(ctx.zhat, ctx.lams, ctx.seff, ctx.nus, dl_dzhat, want=tuple(ctx.needs_input_grad[:6]),
+                                     shared=shared, dl_dlam=dl_dlam, dl_dnu=dl_dnu if neq > 0 else None, want_dz=want_pen)
+            drho = dl1 = None
+            if want_pen:
+                grads, dz = grads[:6], grads[6]
+                # d loss / d l1 = dz / (dt + rho), d loss / d rho = t d loss / d l1; shared: `.mean(0)`, a scalar summed over the rows
+                dgam = dz / (ctx.dt + ctx.rho)
+                if ctx.needs_input_grad[7]:
+                    dl1 = dgam.mean(0) if ctx.l1_dim < 2 else dgam
+                    dl1 = dl1.sum() if ctx.l1_dim == 0 else dl1
+                if ctx.needs_input_grad[6]:
+                    drho = dgam * ctx.t
+                    drho = drho.mean(0) if ctx.rho_dim < 2 else drho
+                    drho = drho.sum() if ctx.rho_dim == 0 else drho
+            if neq == 0:
+                grads = grads[:4] + (None, None)
+            return grads + (drho, dl1)
+
+    def _apply_elastic(Q, p, G, h, A, b, rho, kappa, lower, l1):
+        what = "qpth_amd: l1 (elastic rows)"
+        out = "; write the augmented dense QP in (z, t) instead"
+        if rho is None:
+            raise ValueError(what + " needs rho: rho is the penalty's curvature, gamma't + 1/2 t'diag(rho)t, and the pure l1 penalty "
+                             "(rho = 0, a singular augmented Q) is not served")
+        if kappa is not None:
+            raise ValueError(what + " together with kappa (the barrier-smoothed QP) is not served" + out)
+        if lower is not None:
+            raise ValueError(what + " together with lower (two-sided rows) is not served" + out)
+        if warm_start is not None:
+            raise ValueError(what + " with warm_start is not served" + out)
+        if refine is not None and int(refine) > 0:
+            raise ValueError(what + " with refine=%d is not served: pass refine=0 or refine=None" % int(refine) + out)
+        if solver != QPSolvers.PDIPM_BATCHED:
+            raise ValueError(what + " is served by solver=QPSolvers.PDIPM_BATCHED only" + out)
+        if Q.dtype != torch.float64:
+            raise ValueError(what + " is served for float64 inputs only (the elastic role exists in float64 arithmetic), got %s"
+                             % Q.dtype + out)
+        nineq, nz = G.size(-2), G.size(-1)
+        neq = A.size(-2) if A.nelement() > 0 else 0
+        if not _lib.backend_for(Q).dll.qpx_elastic_supported(_lib.QPX_F64, nz, nineq, neq):
+            raise ValueError(what + " is served up to nz + neq + nineq = 208 (the thread-grid / tile kernels, qpx_elastic_supported); "
+                             "got nz = %d, nineq = %d, neq = %d" % (nz, nineq, neq) + out)
+        nB = extract_nBatch(Q, p, G, h, A, b)
+        return QPElasticFunctionFn.apply(Q, p, G, h, A, b, as_rho(rho, Q, nineq, nB), as_l1(l1, Q, nineq, nB))
+
     def _apply_range(Q, p, G, h, A, b, rho, kappa, lower):
         what = "qpth_amd: lower (two-sided rows)"
         out = "; write the rows as [G; -G] z <= [h; -lower] instead"
@@ -502,7 +635,9 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         kappa = as_kappa(kappa, Q, nineq, extract_nBatch(Q, p, G, h, A, b))
         return QPSmoothFunctionFn.apply(Q, p, G, h, A, b, kappa, loop_eps)
 
-    def apply(Q, p, G, h, A, b, rho=None, kappa=None, lower=None):
+    def apply(Q, p, G, h, A, b, rho=None, kappa=None, lower=None, l1=None):
+        if l1 is not None:
+            return _apply_elastic(Q, p, G, h, A, b, rho, kappa, lower, l1)
         if lower is not None:
             return _apply_range(Q, p, G, h, A, b, rho, kappa, lower)
         if kappa is not None:
