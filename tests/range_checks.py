@@ -91,14 +91,14 @@ def check_reference_parity(env, label, sides, variant=0):
 
 
 # ---------------------------------------------------------------- 2. iteration counts; the stop rule's || G^T e ||
-def oracle_doubled(arrs, i, eps, want_trace=False):
+def oracle_doubled(arrs, i, eps, want_trace=False, maxIter=20):
     from oracle import qp_oracle as orc
     Q, p, G, h, A, b, lower = arrs
     q = np.shape(A)[1] if np.size(A) else 0
     G2, h2, F = R.double(G[i], h[i], lower[i])
     # (one thread: a QP of this size is microseconds of work, and the default pool is sized by the machine's CPU count)
     o = orc.OracleQP(Q[i:i + 1], p[i:i + 1], G2[None], h2[None], A[i:i + 1] if q else None, b[i:i + 1] if q else None, nthreads=1)
-    return o.forward(eps, 20, 3, True, 1, want_trace=want_trace)
+    return o.forward(eps, maxIter, 3, True, 1, want_trace=want_trace)
 
 
 def check_iteration_counts(env, label, sides, variant=0):
@@ -136,6 +136,39 @@ def check_trace_dual_resid(env, label="t1b"):
     note("trace/" + label, worst)
     assert top > 1e-3, top                       # the shift of the start point is there: || G^T e || takes part
     assert worst <= TOL_REF
+
+
+def check_iterates_after_k(env, label, sides="half", ks=(2, 5)):
+    """the range role's PATH: capped at k iterations (eps = 1e-12, the reference's stall counter) its best iterate is the one
+    oracle/qp_oracle reaches on the doubled QP under the same cap, each QP alone -- zhat, both rows' multipliers and slacks,
+    nu as max |a - ref| / max(1, max |ref|), and the same `iters`.  A loop with another direction, centring or step length
+    than the reference's reaches the same optimum by another path: tests/loop_checks.py, check 1, for this role."""
+    from qpth_amd.kkt import KKTFactors
+    arrs = R.range_problem(label, sides)
+    B, n, m, q = R.SHAPES[label]
+    tq = on(arrs, env.dev)
+    worst = 0.0
+    with env.run():
+        fac = KKTFactors.build(tq[0], tq[2], tq[4], B)
+        for k in ks:
+            res = fac.ipm_range(tq[1], tq[3], tq[6], tq[5], eps=1e-12, maxIter=k, stall_policy=1)
+            it = host(res.iters)
+            for i in range(B):
+                x, y, z2, s2, info = oracle_doubled(arrs, i, 1e-12, maxIter=k)
+                assert it[i] == info["iters"][0], (k, i, it, info["iters"])
+                F = np.flatnonzero(np.isfinite(arrs[6][i]))
+                lam, lam_lo = R.split(z2[0], F, m, 0.0)
+                s, s_lo = R.split(s2[0], F, m, np.inf)
+                fin = np.isfinite(s_lo)
+                mine_lo = host(res.slacks_lo)[i]
+                assert np.array_equal(np.isfinite(mine_lo), fin)
+                fig = [close(host(res.zhat)[i], x[0]), close(host(res.lam)[i], lam), close(host(res.lam_lo)[i], lam_lo),
+                       close(host(res.slacks)[i], s), close(np.where(fin, mine_lo, 0.0), np.where(fin, s_lo, 0.0))]
+                if q:
+                    fig.append(close(host(res.nu)[i], y[0]))
+                worst = max([worst] + fig)
+    note("iterates/%s/%s" % (label, sides), worst)
+    assert worst <= TOL_REF, worst
 
 
 # ---------------------------------------------------------------- 3. lower = -inf everywhere is the six-input call

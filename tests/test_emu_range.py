@@ -41,6 +41,11 @@ def test_trace_dual_resid_is_the_doubled_qps():
     C.check_trace_dual_resid(ENV)
 
 
+@pytest.mark.parametrize("label", ["t1b", "t2", "t4", "c4", "box", "g10"])
+def test_iterates_after_k_iterations_are_the_doubled_qps(label):
+    C.check_iterates_after_k(ENV, label, "half")
+
+
 @pytest.mark.parametrize("label", ["t1b", "t4", "c4", "box", "g10"])
 def test_lower_minus_inf_is_the_six_input_call(label):
     C.check_one_sided_equivalence(ENV, label)

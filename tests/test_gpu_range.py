@@ -49,6 +49,11 @@ def test_trace_dual_resid_is_the_doubled_qps(env):
     C.check_trace_dual_resid(env)
 
 
+@pytest.mark.parametrize("label", ["t1b", "t2", "t4", "c4", "box", "g10"])
+def test_iterates_after_k_iterations_are_the_doubled_qps(env, label):
+    C.check_iterates_after_k(env, label, "half")
+
+
 @pytest.mark.parametrize("label", ["t1b", "t4", "c4", "box", "g10"])
 def test_lower_minus_inf_is_the_six_input_call(env, label):
     C.check_one_sided_equivalence(env, label)
