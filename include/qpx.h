@@ -283,7 +283,7 @@ int qpx_jvp(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac,
  * factorisations for: Jacobians of the solution, sensitivity analysis, per-sample gradients (qpth_amd/sensitivity.py).
  * d (B,m) > 0, one per QP.  rx (B,K,n), rs, rz (B,K,m), ry (B,K,q): a QP's K vectors contiguous, row-major; NULL = zeros, but
  * not all of them (ry is ignored when q = 0): QPX_ERR_ARG.  dx (B,K,n) required; ds, dz (B,K,m), dy (B,K,q): NULL = skip.
- * K >= 1 is a run-time argument; K = 1 computes what qpx_factor_solve_kkt computes (refine = 0).  sfac = 0 (shared factors) as
+ * K >= 1 is a run-time argument; K = 1 IS qpx_factor_solve_kkt (refine = 0): the same kernel, the same bits.  sfac = 0 (shared factors) as
  * everywhere.  There is no refinement here.  Served where qpx_multi_supported returns 1 under the calling thread's knob: the
  * thread-grid / tile kernels (nz+neq+nineq <= 208), dtype QPX_F32, QPX_F64 or QPX_F32_WIDE; the large-QP family returns
  * QPX_ERR_UNSUPPORTED (call qpx_factor_solve_kkt K times there).  A breakdown of the factorisation ORs QPX_ST_KKT_BREAKDOWN

@@ -319,6 +319,12 @@ int api_factor_solve_kkt_multi(int io32, int B, int n, int m, int q, int K, void
                                const void* rs, const void* rz, const void* ry, void* dx, void* ds, void* dz, void* dy,
                                int32_t* status, void* stream)
 {
+    // K = 1 IS the single solve (include/qpx.h says it computes what qpx_factor_solve_kkt computes): the same kernel, so the same
+    // bits -- the multi role's block of kKktMultiRB accumulators adds in another order (up to 4e-12 of the solution apart,
+    // tests/kkt_checks.py) and would carry three zero vectors.  The role-0 body skips a NULL ds, dz, dy as the multi role does.
+    if (K == 1)
+        return api_factor_solve_kkt<T>(io32, B, n, m, q, factors, sfac, d, rx, rs, rz, q > 0 ? ry : nullptr, dx, ds, dz, dy, 0,
+                                       nullptr, 0, nullptr, 0, nullptr, 0, status, stream);
     KktArgs<T> a{};
     a.io32 = io32;
     a.B = B; a.n = n; a.m = m; a.q = q; a.K = K; a.fac = (T*)factors; a.fac_stride = (size_t)sfac;

@@ -49,8 +49,9 @@ def kkt_solve(Q, G, A, d, rx, rz, ry):
     return w[:n], w[n:n + m], w[n + m:]
 
 
-def first_backward(arrs, sol, cots):
-    """(dx, dz, dy), each (B, .), of the first backward for cotangents cots = (r_z, r_lam, r_nu) (None = zero)"""
+def first_backward(arrs, sol, cots, solve=None):
+    """(dx, dz, dy), each (B, .), of the first backward for cotangents cots = (r_z, r_lam, r_nu) (None = zero).
+    solve(i, rx, rz, ry) -> (x, z, y): QP i's solve by another route than kkt_solve (tests/kkt_checks.py: the refined one)"""
     zh, lam, sl, nu = [np.asarray(x, np.float64) for x in sol]
     B, n = zh.shape
     m, q = lam.shape[1], nu.shape[1]
@@ -58,7 +59,9 @@ def first_backward(arrs, sol, cots):
     A = _bat(arrs[4], B, 3) if q else np.zeros((B, 0, n))
     r = [np.zeros((B, k)) if g is None else np.asarray(g, np.float64) for g, k in zip(cots, (n, m, q))]
     d = clamp_d(lam, sl)
-    out = [kkt_solve(Q[i], G[i], A[i], d[i], r[0][i], r[1][i], r[2][i]) for i in range(B)]
+    if solve is None:
+        solve = lambda i, rx, rz, ry: kkt_solve(Q[i], G[i], A[i], d[i], rx, rz, ry)      # noqa: E731
+    out = [solve(i, r[0][i], r[1][i], r[2][i]) for i in range(B)]
     return tuple(np.stack([o[k] for o in out]) for k in range(3))
 
 
@@ -70,9 +73,10 @@ def first_grads(sol, bsol):
     return (0.5 * (o(dx, zh) + o(zh, dx)), dx, o(dz, zh) + o(lam, dx), -dz, o(dy, zh) + o(nu, dx), -dy)
 
 
-def second_order(arrs, sol, bsol, W):
+def second_order(arrs, sol, bsol, W, solve=None):
     """{zdot, lamdot, nudot, HQ .. Hb}, each (B, ...), at the solution sol = (zhat, lam, slacks, nu) and the first backward's
-    bsol = (dx, dz, dy), for per-QP cotangents W = (W_Q, W_p, W_G, W_h, W_A, W_b), each (B, ...) or None (zero)"""
+    bsol = (dx, dz, dy), for per-QP cotangents W = (W_Q, W_p, W_G, W_h, W_A, W_b), each (B, ...) or None (zero); solve: as
+    first_backward's"""
     zh, lam, sl, nu = [np.asarray(x, np.float64) for x in sol]
     dx, dz, dy = [np.asarray(x, np.float64) for x in bsol]
     B, n = zh.shape
@@ -82,19 +86,21 @@ def second_order(arrs, sol, bsol, W):
     shapes = ((n, n), (n,), (m, n), (m,), (q, n), (q,))
     WQ, Wp, WG, Wh, WA, Wb = [np.zeros((B,) + s) if w is None else _bat(w, B, len(s) + 1) for w, s in zip(W, shapes)]
     d = clamp_d(lam, sl)
+    if solve is None:
+        solve = lambda i, rx, rz, ry: kkt_solve(Q[i], G[i], A[i], d[i], rx, rz, ry)      # noqa: E731
     out = {k: [] for k in ("zdot", "lamdot", "nudot") + NAMES}
     for i in range(B):
         S = 0.5 * (WQ[i] + WQ[i].T)
         tx = S @ zh[i] + Wp[i] + WG[i].T @ lam[i] + WA[i].T @ nu[i]
         tz = WG[i] @ zh[i] - Wh[i]
         ty = WA[i] @ zh[i] - Wb[i]
-        zd, ld, nd = kkt_solve(Q[i], G[i], A[i], d[i], tx, tz, ty)
+        zd, ld, nd = solve(i, tx, tz, ty)
         a = dz[i] / np.maximum(lam[i], 1e-8)
         u = a * ld
         gz = S @ dx[i] + WG[i].T @ dz[i] + WA[i].T @ dy[i] + G[i].T @ u
         gl = WG[i] @ dx[i] + a * (G[i] @ zd + tz)
         gn = WA[i] @ dx[i]
-        ex, ez, ey = kkt_solve(Q[i], G[i], A[i], d[i], gz, gl, gn)
+        ex, ez, ey = solve(i, gz, gl, gn)
         o = np.outer
         vals = (zd, ld, nd,
                 0.5 * (o(dx[i], zd) + o(zd, dx[i])) + 0.5 * (o(ex, zh[i]) + o(zh[i], ex)), ex,
