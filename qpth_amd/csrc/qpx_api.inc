@@ -158,6 +158,21 @@ int api_pre_factor(int B, int n, int m, int q, const void* Q, int64_t sQ, const 
     return QPX_ERR_UNSUPPORTED;
 }
 
+// the fields every loop entry point fills in the same way (api_ipm, qpx_ipm_range, qpx_ipm_elastic)
+template <class T>
+void ipm_common_args(IpmArgs<T>& a, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh, const void* bb,
+                     int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim, int stall_policy,
+                     void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status, void* best_resid, void* trace)
+{
+    a.B = B; a.n = n; a.m = m; a.q = q;
+    a.p = (const T*)p; a.h = (const T*)h; a.b = (const T*)bb;
+    a.sp = sp; a.sh = sh; a.sb = sb;
+    a.fac = (T*)factors; a.fac_stride = (size_t)sfac;
+    a.eps = (T)eps; a.maxIter = maxIter; a.notImprovedLim = notImprovedLim; a.stall_policy = stall_policy;
+    a.zhat = (T*)zhat; a.nu = (T*)nu; a.lam = (T*)lam; a.slack = (T*)slack;
+    a.iters = iters; a.status = status; a.best_resid = (T*)best_resid; a.trace = (T*)trace;
+}
+
 template <class T>
 int api_ipm(int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
             const void* bb, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
@@ -172,13 +187,8 @@ int api_ipm(int B, int n, int m, int q, const void* p, int64_t sp, const void* h
     if ((lam0 == nullptr) != (s0 == nullptr)) return QPX_ERR_ARG;
     IpmArgs<T> a;
     a.io32 = io32;
-    a.B = B; a.n = n; a.m = m; a.q = q;
-    a.p = (const T*)p; a.h = (const T*)h; a.b = (const T*)bb;
-    a.sp = sp; a.sh = sh; a.sb = sb;
-    a.fac = (T*)factors; a.fac_stride = (size_t)sfac;
-    a.eps = (T)eps; a.maxIter = maxIter; a.notImprovedLim = notImprovedLim; a.stall_policy = stall_policy;
-    a.zhat = (T*)zhat; a.nu = (T*)nu; a.lam = (T*)lam; a.slack = (T*)slack;
-    a.iters = iters; a.status = status; a.best_resid = (T*)best_resid; a.trace = (T*)trace;
+    ipm_common_args(a, B, n, m, q, p, sp, h, sh, bb, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters, status,
+                    best_resid, trace);
     a.lam0 = (const T*)lam0; a.s0 = (const T*)s0; a.warm_floor = (T)warm_floor; a.warm_used = lam0 ? warm_used : nullptr;
     a.images = blob_images<T>(n, m, q);
     if (a.images == 8) {
@@ -424,7 +434,9 @@ inline int api_backward2(KktArgs<double>& a, void* stream)
 // and of the backward (kKktRangeRole), float64 arithmetic.  Which form serves a size follows api_ipm's / api_kkt's rule for
 // float64; a form without the role -- the two-wave tile forms and the small thread-grid forms, reachable through the A/B knob
 // alone -- declines, it never falls through to a kernel that reads another image of the blob.  launch = false: the decision only.
-inline int api_ipm_range(IpmArgs<double>& a, void* stream, bool launch)
+// (kRoleBase: kIpmRangeRole or kIpmElasticRole; kRole: the role's index in the LDS sizes, 1 or 2 -- as ipm_loop_role's)
+template <int kRoleBase, int kRole>
+int api_ipm_role(IpmArgs<double>& a, void* stream, bool launch)
 {
     const int n = a.n, m = a.m, q = a.q;
     if (!use_grid(n, m, q)) return QPX_ERR_UNSUPPORTED;            // the large-QP family has no such role
@@ -434,23 +446,24 @@ inline int api_ipm_range(IpmArgs<double>& a, void* stream, bool launch)
         const int nst = slots_for(n, 16 * nbt, q);
         const int nw = tile_waves(nbt, a.B);
         const bool ch = tile_chain(nbt, nw);
-        const size_t tb = lds_elems_ipm_tile(nbt, nw, n, q, ch, 1) * sizeof(double);
+        const size_t tb = lds_elems_ipm_tile(nbt, nw, n, q, ch, kRole) * sizeof(double);
         if (tb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
 #define QPX_PICK(NBL, NW, NS, CH) \
-        if (nbt == NBL && nw == NW && nst == NS && ch == CH) return launch ? launch_ipm_tile<NBL + kIpmRangeRole, NW, NS, CH>(a, tb, stream) : QPX_OK;
+        if (nbt == NBL && nw == NW && nst == NS && ch == CH) return launch ? launch_ipm_tile<NBL + kRoleBase, NW, NS, CH>(a, tb, stream) : QPX_OK;
         QPX_FORMS_IPM_RANGE_TILE(QPX_PICK)
 #undef QPX_PICK
         return QPX_ERR_UNSUPPORTED;
     }
     const int nbg = grid_nb(m);
     const int nsg = slots_for(n, 16 * nbg, q);
-    const size_t gb = lds_elems_ipm_grid(16, nbg, n, q, 1) * sizeof(double);
+    const size_t gb = lds_elems_ipm_grid(16, nbg, n, q, kRole) * sizeof(double);
     if (gb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
-#define QPX_PICK(NBL, NS) if (nbg == NBL && nsg == NS) return launch ? launch_ipm_grid<double, NBL + kIpmRangeRole, NS>(a, gb, stream) : QPX_OK;
+#define QPX_PICK(NBL, NS) if (nbg == NBL && nsg == NS) return launch ? launch_ipm_grid<double, NBL + kRoleBase, NS>(a, gb, stream) : QPX_OK;
     QPX_FORMS_IPM_RANGE_GRID(QPX_PICK)
 #undef QPX_PICK
     return QPX_ERR_UNSUPPORTED;
 }
+inline int api_ipm_range(IpmArgs<double>& a, void* stream, bool launch) { return api_ipm_role<kIpmRangeRole, 1>(a, stream, launch); }
 inline int api_backward_range(KktArgs<double>& a, void* stream, bool launch)
 {
     const int n = a.n, m = a.m, q = a.q;
@@ -486,33 +499,7 @@ inline bool range_served(int dtype, int n, int m, int q, int B)
 
 // Elastic rows (qpx_ipm_elastic; DESIGN 4.12): the elastic role of the same loop forms (qpx_forms.h: kIpmElasticRole), picked by
 // api_ipm_range's rule; the backward runs on the hard factors as it stands.  A form without the role declines.
-inline int api_ipm_elastic(IpmArgs<double>& a, void* stream, bool launch)
-{
-    const int n = a.n, m = a.m, q = a.q;
-    if (!use_grid(n, m, q)) return QPX_ERR_UNSUPPORTED;            // the large-QP family has no such role
-    a.images = blob_images<double>(n, m, q);
-    if (a.images == 4) {
-        const int nbt = tile_nb(m);
-        const int nst = slots_for(n, 16 * nbt, q);
-        const int nw = tile_waves(nbt, a.B);
-        const bool ch = tile_chain(nbt, nw);
-        const size_t tb = lds_elems_ipm_tile(nbt, nw, n, q, ch, 2) * sizeof(double);
-        if (tb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
-#define QPX_PICK(NBL, NW, NS, CH) \
-        if (nbt == NBL && nw == NW && nst == NS && ch == CH) return launch ? launch_ipm_tile<NBL + kIpmElasticRole, NW, NS, CH>(a, tb, stream) : QPX_OK;
-        QPX_FORMS_IPM_RANGE_TILE(QPX_PICK)
-#undef QPX_PICK
-        return QPX_ERR_UNSUPPORTED;
-    }
-    const int nbg = grid_nb(m);
-    const int nsg = slots_for(n, 16 * nbg, q);
-    const size_t gb = lds_elems_ipm_grid(16, nbg, n, q, 2) * sizeof(double);
-    if (gb > lds_budget_bytes()) return QPX_ERR_UNSUPPORTED;
-#define QPX_PICK(NBL, NS) if (nbg == NBL && nsg == NS) return launch ? launch_ipm_grid<double, NBL + kIpmElasticRole, NS>(a, gb, stream) : QPX_OK;
-    QPX_FORMS_IPM_RANGE_GRID(QPX_PICK)
-#undef QPX_PICK
-    return QPX_ERR_UNSUPPORTED;
-}
+inline int api_ipm_elastic(IpmArgs<double>& a, void* stream, bool launch) { return api_ipm_role<kIpmElasticRole, 2>(a, stream, launch); }
 // (B: the batch the tile forms' waves per QP depend on)
 inline bool elastic_served(int dtype, int n, int m, int q, int B)
 {
@@ -926,13 +913,8 @@ int qpx_ipm_range(int dtype, int B, int n, int m, int q, const void* p, int64_t 
     if (maxIter < 0 || stall_policy < 0 || stall_policy > 2 || slo < 0) return QPX_ERR_ARG;
     if (!qpx::range_served(dtype, n, m, q, B)) return QPX_ERR_UNSUPPORTED;
     qpx::IpmArgs<double> a{};
-    a.B = B; a.n = n; a.m = m; a.q = q;
-    a.p = (const double*)p; a.h = (const double*)h; a.b = (const double*)b;
-    a.sp = sp; a.sh = sh; a.sb = sb;
-    a.fac = (double*)factors; a.fac_stride = (size_t)sfac;
-    a.eps = eps; a.maxIter = maxIter; a.notImprovedLim = notImprovedLim; a.stall_policy = stall_policy;
-    a.zhat = (double*)zhat; a.nu = (double*)nu; a.lam = (double*)lam; a.slack = (double*)slack;
-    a.iters = iters; a.status = status; a.best_resid = (double*)best_resid; a.trace = (double*)trace;
+    qpx::ipm_common_args(a, B, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters,
+                         status, best_resid, trace);
     a.lower = (const double*)lower; a.slo = slo; a.gt1 = (const double*)gt1;
     a.lam_lo = (double*)lam_lo; a.slack_lo = (double*)slack_lo;
     return qpx::api_ipm_range(a, stream, true);
@@ -981,13 +963,8 @@ int qpx_ipm_elastic(int dtype, int B, int n, int m, int q, const void* p, int64_
     if (maxIter < 0 || stall_policy < 0 || stall_policy > 2 || sgamma < 0 || srho < 0) return QPX_ERR_ARG;
     if (!qpx::elastic_served(dtype, n, m, q, B)) return QPX_ERR_UNSUPPORTED;
     qpx::IpmArgs<double> a{};
-    a.B = B; a.n = n; a.m = m; a.q = q;
-    a.p = (const double*)p; a.h = (const double*)h; a.b = (const double*)b;
-    a.sp = sp; a.sh = sh; a.sb = sb;
-    a.fac = (double*)factors; a.fac_stride = (size_t)sfac;
-    a.eps = eps; a.maxIter = maxIter; a.notImprovedLim = notImprovedLim; a.stall_policy = stall_policy;
-    a.zhat = (double*)zhat; a.nu = (double*)nu; a.lam = (double*)lam; a.slack = (double*)slack;
-    a.iters = iters; a.status = status; a.best_resid = (double*)best_resid; a.trace = (double*)trace;
+    qpx::ipm_common_args(a, B, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters,
+                         status, best_resid, trace);
     a.gamma = (const double*)gamma; a.sgamma = sgamma; a.rho = (const double*)rho; a.srho = srho; a.gt1 = (const double*)gt1;
     a.lam_lo = (double*)lam_t; a.slack_lo = (double*)slack_t; a.tviol = (double*)t;
     return qpx::api_ipm_elastic(a, stream, true);

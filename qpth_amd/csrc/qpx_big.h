@@ -911,7 +911,8 @@ template <class T> QPX_DEV void big_symv_body(const Block& b, const BigSymvArgs<
 
 // ------------------------------------------------------------------------------------------ loop phases
 // The vector work of the PDIPM loop: one wave per QP on the blob's vectors (NS = MP / 64 register slots).  The
-// mathematics and the control flow are those of ipm_loop_body (qpx_grid.h), phase by phase:
+// mathematics and the control flow are those of ipm_loop_body (qpx_grid.h), phase by phase; phases 1, 3 and 4 ARE its blocks
+// (ipm_start_point, ipm_affine_step, ipm_final_step) on the blob's vectors:
 //   0  initialise the state (z = s = 1, tau = 1, ...), stage p and c's constant part
 //   1  start point: x = -T^-1 c is in vX -> shifts, z, s, best := start, vA = z'
 //   2  residuals with vB = R z', best iterate, stop decision, d = s/z, affine right-hand side
@@ -1009,27 +1010,7 @@ template <class T, int NS> QPX_DEV void big_phase_body(const Block& b, const Big
         return;
     }
     if (a.phase == 1) {
-        T x[NS];
-        ld_slots<NS>(b, x, vX, m, T(0));
-        T mnz = Lim<T>::inf(), mns = Lim<T>::inf();
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const int i = k * kWave + lane;
-            if (i < m) { mnz = min2_(mnz, x[k]); mns = min2_(mns, -x[k]); }
-        }
-        mnz = wave_min(b, mnz);
-        mns = wave_min(b, mns);
-        const T sigz = (mnz < T(0)) ? (T(1) - mnz) : T(0);
-        const T sigs = (mns < T(0)) ? (T(1) - mns) : T(0);
-        if (lane == 0) { sc[bsSigz] = sigz; sc[bsSigs] = sigs; }
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const int i = k * kWave + lane;
-            if (i < m) {
-                const T zk = x[k] + sigz, sk = -x[k] + sigs;
-                vZ[i] = zk; vS[i] = sk; vA[i] = x[k]; vBZ[i] = zk; vBS[i] = sk;
-            }
-        }
+        ipm_start_point<T, NS>(b, lane, m, m, vX, vZ, vS, vA, vBZ, vBS, sc + bsSigz, sc + bsSigs);      // (M8 = m: no pad is written)
         return;
     }
     if (a.phase == 7) {
@@ -1115,78 +1096,11 @@ template <class T, int NS> QPX_DEV void big_phase_body(const Block& b, const Big
         return;
     }
     if (a.phase == 3) {
-        const T mu = sc[bsMu], szdot = sc[bsSzdot];
-        T z[NS], s[NS], rz[NS], rsv[NS], dd[NS], dza[NS], dsa[NS];
-        ld_slots<NS>(b, z, vZ, m, T(1));
-        ld_slots<NS>(b, s, vS, m, T(1));
-        ld_slots<NS>(b, rz, vRZ, m, T(1));
-        ld_slots<NS>(b, rsv, vRS, m, T(1));
-        ld_slots<NS>(b, dd, vD, m, T(1));
-        ld_slots<NS>(b, dza, vX, m, T(0));
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const int i = k * kWave + lane;
-            dsa[k] = (i < m) ? (-s[k] - dza[k] * dd[k]) : T(0);
-        }
-        T al = step_to_boundary_rcp<NS>(b, rz, dza, m);
-        const T al2 = step_to_boundary_rcp<NS>(b, rsv, dsa, m);
-        al = min2_(al, al2);
-        al = min2_(al, T(1));
-        T t3 = 0;
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const int i = k * kWave + lane;
-            if (i < m) t3 = fma_(s[k] + al * dsa[k], z[k] + al * dza[k], t3);
-        }
-        t3 = wave_sum(b, t3);
-        T sig = t3 / szdot;
-        sig = sig * sig * sig;
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const int i = k * kWave + lane;
-            if (i < m) {
-                const T rs = (-mu * sig + dsa[k] * dza[k]) * rsv[k];
-                vRSC[i] = rs;
-                vRH[i] = rs * dd[k];
-                vDZA[i] = dza[k];
-                vDSA[i] = dsa[k];
-            }
-        }
+        ipm_affine_step<T, NS>(b, lane, m, sc[bsMu], sc[bsSzdot], vZ, vS, vRZ, vRS, vD, vX, vRSC, vRH, vDZA, vDSA);
         return;
     }
     if (a.phase == 4) {
-        T z[NS], s[NS], rz[NS], rsv[NS], dz[NS], ds[NS];
-        ld_slots<NS>(b, z, vZ, m, T(1));
-        ld_slots<NS>(b, s, vS, m, T(1));
-        ld_slots<NS>(b, rz, vRZ, m, T(1));
-        ld_slots<NS>(b, rsv, vRS, m, T(1));
-        ld_slots<NS>(b, dz, vX, m, T(0));
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const int i = k * kWave + lane;
-            const T dsc = (i < m) ? ((-vRSC[i] - dz[k]) * vD[i]) : T(0);
-            dz[k] = (i < m) ? (vDZA[i] + dz[k]) : T(0);
-            ds[k] = (i < m) ? (vDSA[i] + dsc) : T(0);
-        }
-        T al = step_to_boundary_rcp<NS>(b, rz, dz, m);
-        const T al3 = step_to_boundary_rcp<NS>(b, rsv, ds, m);
-        al = min2_(al, al3);
-        al = T(0.999) * al;
-        al = min2_(al, T(1));
-        const T tau = (T(1) - al) * sc[bsTau];
-        const T tsz = tau * sc[bsSigz];
-        b.wave_sync();
-        if (lane == 0) { sc[bsTau] = tau; sc[bsAlphaPrev] = al; }
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const int i = k * kWave + lane;
-            if (i < m) {
-                const T zk = fma_(al, dz[k], z[k]);
-                vZ[i] = zk;
-                vS[i] = fma_(al, ds[k], s[k]);
-                vA[i] = zk - tsz;
-            }
-        }
+        ipm_final_step<T, NS>(b, lane, m, vZ, vS, vRZ, vRS, vD, vX, vRSC, vDZA, vDSA, vA, sc + bsTau, sc + bsAlphaPrev, sc[bsSigz]);
         return;
     }
 }

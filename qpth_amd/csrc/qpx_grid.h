@@ -790,7 +790,8 @@ QPX_LAYOUT_HD size_t lds_elems_sweep(int nbl) { return (size_t)3 * 16 * nbl + 8 
 
 // ------------------------------------------------------------------------------------------
 // The O(m) vector blocks of the PDIPM loop, by ONE wave on LDS-resident vectors (a vector of length m is NS slots of 64
-// lanes); shared by the two orders of a pass in ipm_loop_role.
+// lanes); shared by the two orders of a pass in ipm_loop_role and by the large-QP family's phase kernel (qpx_big.h), whose
+// vectors are in the blob.
 // Start point (batch.py:61-87): vX = -T^-1 c -> z, s shifted to >= 1 where their minimum is negative; z' = x
 template <class T, int NS>
 QPX_DEV void ipm_start_point(const Block& b, int lane, int m, int M8, const T* vX, T* vZ, T* vS, T* vA, T* vBZ, T* vBS, T* pSigz, T* pSigs)

@@ -251,7 +251,6 @@ QPX_LAYOUT_HD size_t max2(size_t a, size_t b) { return a > b ? a : b; }
 // step length to the boundary for one QP (get_step, batch.py:210-213, as it behaves for a batch of one): min over blocking
 // entries of -v/dv, or 1 when nothing blocks -- from the reciprocals rv = 1/v the caller already holds: the minimum of -v/dv
 // is the reciprocal of the maximum of -dv/v, so the per-entry divisions become multiplications and
-// is the reciprocal of the maximum of -dv/v, so the per-entry divisions become multiplications and
 // one division remains (f64 division is a ~15-instruction sequence on gfx950).
 template <int NS, class T>
 QPX_DEV T step_to_boundary_rcp(const Block& b, const T (&rv)[NS], const T (&dv)[NS], int m)

@@ -85,6 +85,14 @@ static void one(int dt, int B, int n, int m, int q, int knob)
     std::printf(" backward -> %d\n", e);
     e = qpx_jvp(dt, B, n, m, q, P(4), fe, P(9), P(11), P(12), P(10), P(31), (int64_t)n * n, P(32), n, P(33), (int64_t)m * n, P(34), m, P(35), (int64_t)q * n, P(36), q, P(37), P(38), P(39), P(40), 0, P(1), (int64_t)n * n, P(2), (int64_t)m * n, P(3), (int64_t)q * n, (int32_t*)P(5), st);
     std::printf(" jvp -> %d\n", e);
+    // the warm entry and the range / elastic roles of the loop forms (their LDS bytes carry the role's vectors)
+    std::printf("# warm=%d range=%d elastic=%d\n", qpx_warm_supported(dt, n, m, q), qpx_range_supported(dt, n, m, q), qpx_elastic_supported(dt, n, m, q));
+    e = qpx_ipm_warm(dt, B, n, m, q, P(6), n, P(7), m, P(8), q, P(4), fe, 1e-12, 2, 3, 2, P(9), P(10), P(11), P(12), (int32_t*)P(13), (int32_t*)P(5), P(14), nullptr, P(41), P(42), 1e-2, (int32_t*)P(43), st);
+    std::printf(" ipm_warm -> %d\n", e);
+    e = qpx_ipm_range(dt, B, n, m, q, P(6), n, P(7), m, P(8), q, P(4), fe, 1e-12, 2, 3, 2, P(9), P(10), P(11), P(12), (int32_t*)P(13), (int32_t*)P(5), P(14), nullptr, P(44), m, P(45), P(46), P(47), st);
+    std::printf(" ipm_range -> %d\n", e);
+    e = qpx_ipm_elastic(dt, B, n, m, q, P(6), n, P(7), m, P(8), q, P(4), fe, 1e-12, 2, 3, 2, P(9), P(10), P(11), P(12), (int32_t*)P(13), (int32_t*)P(5), P(14), nullptr, P(44), m, P(48), m, P(45), P(46), P(47), P(49), st);
+    std::printf(" ipm_elastic -> %d\n", e);
     e = qpx_polish(dt, B, n, m, q, P(1), (int64_t)n * n, P(6), n, P(2), (int64_t)m * n, P(7), m, P(3), (int64_t)q * n, P(8), q, P(4), fe, 2, 0, P(9), P(10), P(11), P(12), P(14), (int32_t*)P(5), st);
     std::printf(" polish -> %d\n", e);
     qpx_set_ipm_variant(0);
