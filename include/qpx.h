@@ -428,6 +428,38 @@ int qpx_ipm_elastic(int dtype, int B, int n, int m, int q, const void* p, int64_
                     void* best_resid, void* trace, const void* gamma, int64_t sgamma, const void* rho, int64_t srho,
                     const void* gt1, void* lam_t, void* slack_t, void* t, qpx_stream_t stream);
 
+/* Additive after v8 (QPX_ABI_VERSION stays 8): SOFT TWO-SIDED inequality rows,
+ *   min 1/2 z'Qz + p'z + sum_i ( gu_i tu_i + 1/2 ru_i tu_i^2 + gl_i tl_i + 1/2 rl_i tl_i^2 )
+ *   s.t.  l - tl <= G z <= h + tu,  tu, tl >= 0,  A z = b
+ * -- the QP a caller had to write with nz + 2 nineq variables and 4 nineq rows.  The factors are those of qpx_pre_factor for
+ * (Q, G, A), the HARD QP's: the augmented QP's Newton system collapses to the m x m system the loop already factors, with the
+ * diagonal 1/(1/e_u + 1/e_l), e = s/lam + 1/(rho + lam_t/slack_t) on a soft side, s/lam on a hard one, 1/e_l = 0 on a one-sided
+ * row; the iterates, iteration counts and stop rule are those of qpx_ipm on the augmented QP.
+ * qpx_ipm_soft_range: qpx_ipm's arguments, then
+ *   lower (B,m), batch stride slo (0 = one (m) vector): -inf = a one-sided row, otherwise lower < h strictly;
+ *   gamma_u, rho_u, gamma_l, rho_l (B,m) with batch strides: the penalty of each side; gamma = +inf or rho = +inf makes that
+ *     side HARD; otherwise gamma >= 0 and rho > 0.  The lower side's entries of a one-sided row are checked and otherwise unused;
+ *   gt1 (B): sqrt(|| G^T e ||^2 + 4 (k_u + k_l)) per QP, e_i = 1 on one-sided rows and 0 on two-sided ones, k the number of soft
+ *     sides -- the augmented QP's || G'^T 1 || of the stop rule;
+ *   lam_lo, slack_lo: the lower rows' multipliers and slacks; lam_t, slack_t, t / lam_tl, slack_tl, t_lo: those of tu >= 0 /
+ *     tl >= 0 and tu / tl themselves, all (B,m), out; an absent side reads 0, +inf and 0.
+ * status: a NaN entry, a lower not below h, a negative gamma or a rho that is not positive ORs QPX_ST_NONFINITE and the QP is
+ * left as after a failed pre-factorisation: NaN in the outputs, iters = 0, best_resid = +inf.  trace as in qpx_ipm; mu is the
+ * augmented QP's (over all live complementarity pairs).
+ * The backward is qpx_backward_range on the same factors, given lam, lam_lo and the EFFECTIVE slack of each side,
+ *   slack_eff = clamp(lam) (clamp(slack)/clamp(lam) + 1/(rho + clamp(lam_t)/clamp(slack_t)))      (slack on a hard side).
+ * Served in float64 arithmetic by the loop forms the default dispatch picks, nz+neq+nineq <= 208 (qpx_soft_range_supported);
+ * QPX_F32, QPX_F32_WIDE, the large-QP family and forms reachable through the A/B knob alone: QPX_ERR_UNSUPPORTED.  No warm
+ * start and no soft factors in this role. */
+int qpx_soft_range_supported(int dtype, int n, int m, int q);
+int qpx_ipm_soft_range(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
+                       const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
+                       int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
+                       void* best_resid, void* trace, const void* lower, int64_t slo, const void* gamma_u, int64_t sgamma_u,
+                       const void* rho_u, int64_t srho_u, const void* gamma_l, int64_t sgamma_l, const void* rho_l,
+                       int64_t srho_l, const void* gt1, void* lam_lo, void* slack_lo, void* lam_t, void* slack_t, void* lam_tl,
+                       void* slack_tl, void* t, void* t_lo, qpx_stream_t stream);
+
 /* Batch-MEAN of the gradient of a parameter that the whole batch shares (qp.py:159-177: the reference
  * forms B outer products and then `.mean(0)`): one contraction over the batch instead,
  *   out (r,c) = scale/B * sum_b ( u[b][r] v[b][c] + w[b][r] x[b][c] )        u, w: (B,r)  v, x: (B,c)

@@ -75,6 +75,10 @@ _SIGNATURES = {
     "qpx_elastic_supported": (_i, [_i, _i, _i, _i]),
     "qpx_ipm_elastic": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d, _i, _i, _i,
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "qpx_soft_range_supported": (_i, [_i, _i, _i, _i]),
+    "qpx_ipm_soft_range": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d, _i, _i, _i,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qpx_batch_outer": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, ctypes.c_size_t, _vp]),
     "qpx_batch_outer_workspace_elems": (ctypes.c_size_t, [_i, _i, _i, _i]),
     "qpx_dense_solve": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -265,6 +269,22 @@ class QpxLib:
             _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
             _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid), _ptr(trace),
             gp.ptr, gp.stride, rp.ptr, rp.stride, _ptr(gt1), _ptr(lam_t), _ptr(slack_t), _ptr(t), _stream(factors)))
+
+    # -- soft two-sided rows lower - tl <= G z <= h + tu: the loop's soft-range role, float64
+    def ipm_soft_range(self, B, n, m, q, p, h, lower, gamma_u, rho_u, gamma_l, rho_l, gt1, b, factors, sfac, eps, maxIter,
+                       notImprovedLim, stall_policy, zhat, nu, lam, slack, lam_lo, slack_lo, lam_t, slack_t, lam_tl, slack_tl,
+                       t, t_lo, iters, status, best_resid, trace=None):
+        """lower and the four penalty vectors (B,m), (1,m) or (m,) (shared: batch stride 0); -inf in lower = a one-sided row,
+        +inf in a side's gamma or rho = a hard side; gt1 (B,) = || G'^T 1 ||"""
+        pp, hp, bp, lp = Param(p, 2), Param(h, 2), Param(b, 2), Param(lower, 2)
+        gu, ru, gl, rl = Param(gamma_u, 2), Param(rho_u, 2), Param(gamma_l, 2), Param(rho_l, 2)
+        self.check(self.dll.qpx_ipm_soft_range(
+            _dtype_code(factors), B, n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
+            _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
+            _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid), _ptr(trace),
+            lp.ptr, lp.stride, gu.ptr, gu.stride, ru.ptr, ru.stride, gl.ptr, gl.stride, rl.ptr, rl.stride, _ptr(gt1),
+            _ptr(lam_lo), _ptr(slack_lo), _ptr(lam_t), _ptr(slack_t), _ptr(lam_tl), _ptr(slack_tl), _ptr(t), _ptr(t_lo),
+            _stream(factors)))
 
     # -- forward mode (QPFunctionFn.jvp): the tangent of the solution, one KKT solve with the backward's matrix
     def jvp(self, B, n, m, q, factors, sfac, zhat, lam, slack, nu, tQ, tp, tG, th, tA, tb, dzhat, status,

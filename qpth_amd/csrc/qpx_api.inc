@@ -434,7 +434,8 @@ inline int api_backward2(KktArgs<double>& a, void* stream)
 // and of the backward (kKktRangeRole), float64 arithmetic.  Which form serves a size follows api_ipm's / api_kkt's rule for
 // float64; a form without the role -- the two-wave tile forms and the small thread-grid forms, reachable through the A/B knob
 // alone -- declines, it never falls through to a kernel that reads another image of the blob.  launch = false: the decision only.
-// (kRoleBase: kIpmRangeRole or kIpmElasticRole; kRole: the role's index in the LDS sizes, 1 or 2 -- as ipm_loop_role's)
+// (kRoleBase: kIpmRangeRole, kIpmElasticRole or kIpmSoftRangeRole; kRole: the role's index in the LDS sizes, 1, 2 or 3 -- as
+// ipm_loop_role's)
 template <int kRoleBase, int kRole>
 int api_ipm_role(IpmArgs<double>& a, void* stream, bool launch)
 {
@@ -507,6 +508,21 @@ inline bool elastic_served(int dtype, int n, int m, int q, int B)
     IpmArgs<double> ia{};
     ia.B = B; ia.n = n; ia.m = m; ia.q = q;
     return api_ipm_elastic(ia, nullptr, false) == QPX_OK;
+}
+
+// Soft two-sided rows (qpx_ipm_soft_range; DESIGN 4.13): the soft-range role of the same loop forms (kIpmSoftRangeRole), picked
+// by api_ipm_range's rule; the backward is the range role's (api_backward_range) with effective slacks.  A form without the role
+// declines, and so does one whose 49 vectors do not fit the LDS budget.
+inline int api_ipm_soft_range(IpmArgs<double>& a, void* stream, bool launch) { return api_ipm_role<kIpmSoftRangeRole, 3>(a, stream, launch); }
+// (B: the batch the tile forms' waves per QP depend on)
+inline bool soft_range_served(int dtype, int n, int m, int q, int B)
+{
+    if (dtype != QPX_F64) return false;
+    IpmArgs<double> ia{};
+    ia.B = B; ia.n = n; ia.m = m; ia.q = q;
+    KktArgs<double> ka{};
+    ka.B = B; ka.n = n; ka.m = m; ka.q = q;
+    return api_ipm_soft_range(ia, nullptr, false) == QPX_OK && api_backward_range(ka, nullptr, false) == QPX_OK;
 }
 
 // the finishing stage: every family has it (thread-grid / tile kernels: one kernel, the blob's register image of R decides the
@@ -968,6 +984,42 @@ int qpx_ipm_elastic(int dtype, int B, int n, int m, int q, const void* p, int64_
     a.gamma = (const double*)gamma; a.sgamma = sgamma; a.rho = (const double*)rho; a.srho = srho; a.gt1 = (const double*)gt1;
     a.lam_lo = (double*)lam_t; a.slack_lo = (double*)slack_t; a.tviol = (double*)t;
     return qpx::api_ipm_elastic(a, stream, true);
+}
+
+int qpx_soft_range_supported(int dtype, int n, int m, int q)
+{
+    if (qpx::check_dims(dtype, 1, n, m, q) != QPX_OK) return 0;
+    // (a small and a large batch cover both choices of the tile forms' waves per QP)
+    return qpx::soft_range_served(dtype, n, m, q, 1) && qpx::soft_range_served(dtype, n, m, q, 1 << 20) ? 1 : 0;
+}
+
+int qpx_ipm_soft_range(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
+                       const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
+                       int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
+                       void* best_resid, void* trace, const void* lower, int64_t slo, const void* gamma_u, int64_t sgamma_u,
+                       const void* rho_u, int64_t srho_u, const void* gamma_l, int64_t sgamma_l, const void* rho_l,
+                       int64_t srho_l, const void* gt1, void* lam_lo, void* slack_lo, void* lam_t, void* slack_t, void* lam_tl,
+                       void* slack_tl, void* t, void* t_lo, qpx_stream_t stream)
+{
+    const int e = qpx::check_dims(dtype, B, n, m, q);
+    if (e) return e;
+    if (!p || !h || !lower || !gamma_u || !rho_u || !gamma_l || !rho_l || !gt1 || !factors || !zhat || !lam || !slack || !lam_lo ||
+        !slack_lo || !lam_t || !slack_t || !lam_tl || !slack_tl || !t || !t_lo || !iters || !status || !best_resid ||
+        (q > 0 && (!nu || !b)))
+        return QPX_ERR_ARG;
+    if (maxIter < 0 || stall_policy < 0 || stall_policy > 2 || slo < 0 || sgamma_u < 0 || srho_u < 0 || sgamma_l < 0 || srho_l < 0)
+        return QPX_ERR_ARG;
+    if (!qpx::soft_range_served(dtype, n, m, q, B)) return QPX_ERR_UNSUPPORTED;
+    qpx::IpmArgs<double> a{};
+    qpx::ipm_common_args(a, B, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters,
+                         status, best_resid, trace);
+    a.lower = (const double*)lower; a.slo = slo; a.gt1 = (const double*)gt1;
+    a.gamma = (const double*)gamma_u; a.sgamma = sgamma_u; a.rho = (const double*)rho_u; a.srho = srho_u;
+    a.gamma_lo = (const double*)gamma_l; a.sgamma_lo = sgamma_l; a.rho_lo = (const double*)rho_l; a.srho_lo = srho_l;
+    a.lam_lo = (double*)lam_lo; a.slack_lo = (double*)slack_lo;
+    a.lam_t = (double*)lam_t; a.slack_t = (double*)slack_t; a.lam_tl = (double*)lam_tl; a.slack_tl = (double*)slack_tl;
+    a.tviol = (double*)t; a.tviol_lo = (double*)t_lo;
+    return qpx::api_ipm_soft_range(a, stream, true);
 }
 
 int qpx_polish_supported(int dtype, int n, int m, int q)

@@ -62,6 +62,13 @@ constexpr int kKktRangeRole = 256;
 // slack the host forms.
 constexpr int kIpmElasticRole = 128;
 
+// Soft two-sided rows l - tl <= G z <= h + tu, tu, tl >= 0 with a penalty gamma t + 1/2 rho t^2 per side (qpx_ipm_soft_range;
+// DESIGN 4.13), float64 arithmetic only: the composition of the two roles above.  The same loop forms exist a fourth time as the
+// SOFT-RANGE role (qpx_grid.h: ipm_loop_role, kSoft): blocks / tile rows + kIpmSoftRangeRole in the form's FIRST parameter; the
+// one-sided, range and elastic forms hold none of its code.  The backward runs in the range role (kKktRangeRole) with an
+// effective slack per side the host forms.
+constexpr int kIpmSoftRangeRole = kIpmRangeRole | kIpmElasticRole;
+
 }  // namespace qpx
 
 // thread-grid kernels: (blocks of 16 -- of 8 in the one-wave grid -- per side), (blocks, slots of 64 columns)

@@ -279,7 +279,8 @@ QPX_LAYOUT_HD size_t lds_elems_ipm_loop(size_t mp, size_t scratch, int n, int q,
 {
     const size_t d = max2(max2((size_t)n, mp), (size_t)q);
     const size_t v = d <= 64 ? 64 : (d <= 128 ? 128 : (d <= 256 ? 256 : 512));    // 64 NS, see ipm_loop_body
-    return (role == 2 ? 28 : (role == 1 ? 27 : 17)) * v + 24 + scratch;
+    // (role 3, the soft-range role: the range role's ten, sixteen of the two t-sides, two of t itself, four of the penalties)
+    return (role == 3 ? 49 : (role == 2 ? 28 : (role == 1 ? 27 : 17))) * v + 24 + scratch;
 }
 QPX_LAYOUT_HD size_t lds_elems_ipm_grid(int gs, int nbl, int n, int q, int role = 0)
 {
@@ -1315,15 +1316,423 @@ QPX_DEV void elastic_final_step(const Block& b, int lane, int m, const T* vGam, 
 }
 
 // ------------------------------------------------------------------------------------------
+// The same blocks for SOFT TWO-SIDED rows l_i - tl_i <= g_i'z <= h_i + tu_i, tu, tl >= 0 with a penalty gamma t + 1/2 rho t^2 on
+// each side (the loop's soft-range role): the composition of the two sets above.  The reference's QP has the
+// variables (z, tu, tl) and the rows [G, -E, 0; -G_L, 0, -E; 0, -I, 0; 0, 0, -I] (z, tu, tl) <= (h, -l_L, 0, 0).  Per side
+// (u, l) with w = z/s, wt = zt/st: a soft side has e = 1/(rho + wt) and the effective weight W = 1/(1/w + e), a hard side e = 0
+// and W = w, a one-sided row Wl = 0.  Eliminating each t-side as the elastic role does leaves the range role's system in W,
+//   (R + diag(1/(Wu + Wl))) v = -(Wu qu~ - Wl ql~)/(Wu + Wl),   dzu = Wu (-qu~ - R v),   dzl = Wl (-ql~ + R v),
+//   q~ = q - wt e qt,   dzt = -wt e (rho qt + dz),   dst = -st + e (rho qt + dz)      (each side with its own dz),
+// affine step: qu = c + R y, ql = (h - l) - qu, rho qt = z + zt - gamma, so q~ = q + e (z + zt - gamma); corrector: q = rs/w,
+// qt = rst/wt, so q~ = rs/w - e rst, dzt = -e (rho rst + wt dz), dst = -e (rst - dz).  The side with the smaller W goes by its
+// own formula and the other from v (the rule of the range role, with W for w).  A row that is hard on both sides runs the
+// range role's operations, a one-sided row the elastic role's (the one-sided loop's when it is hard).  vRho / vRhoL mark the
+// soft sides (+inf: hard, and vRhoL = +inf on a one-sided row); 1/z, 1/s of all four pairs and vD are formed where the iterate is.
+template <class T> struct SoftVecs {
+    T *vH, *vC, *vD, *vA, *vX, *vRH, *vRSC, *vQUL;
+    T *vZ, *vS, *vRZ, *vRS, *vBZ, *vBS, *vDZA, *vDSA;                       // the upper rows
+    T *vZL, *vSL, *vRZL, *vRSL, *vBZL, *vBSL, *vDZAL, *vDSAL;               // the lower rows
+    T *vZT, *vST, *vRZT, *vRST, *vBZT, *vBST, *vDZAT, *vDSAT;               // tu >= 0
+    T *vZTL, *vSTL, *vRZTL, *vRSTL, *vBZTL, *vBSTL, *vDZATL, *vDSATL;       // tl >= 0
+    T *vQT, *vQTL;            // tu, tl from the block that forms an iterate to the next pass's residuals; rst of each side from the affine step to the combined one
+    T *vGam, *vRho, *vGamL, *vRhoL;
+};
+template <class T> QPX_DEV T soft_e_(bool f, T rho, T zt, T rst) { return f ? rcp_(rho + zt * rst) : T(0); }
+template <class T> QPX_DEV T soft_w_(bool f, T z, T s, T rz, T rs, T e) { return f ? rcp_(s * rz + e) : z * rs; }
+// the reciprocals and the diagonal of the iterate of row i
+template <class T>
+QPX_DEV void softrange_recips(const SoftVecs<T>& V, bool f2, bool fu, bool fl, int i, T zu, T su, T zl, T sl, T ztu, T stu, T ztl, T stl)
+{
+    const T rzu = rcp_(zu), rsu = rcp_(su);
+    V.vRZ[i] = rzu;
+    V.vRS[i] = rsu;
+    T eu = T(0);
+    if (fu) {
+        const T rzt = rcp_(ztu), rst = rcp_(stu);
+        V.vRZT[i] = rzt;
+        V.vRST[i] = rst;
+        eu = rcp_(V.vRho[i] + ztu * rst);
+    }
+    if (f2) {
+        const T rzl = rcp_(zl), rsl = rcp_(sl);
+        V.vRZL[i] = rzl;
+        V.vRSL[i] = rsl;
+        T el = T(0);
+        if (fl) {
+            const T rzt = rcp_(ztl), rst = rcp_(stl);
+            V.vRZTL[i] = rzt;
+            V.vRSTL[i] = rst;
+            el = rcp_(V.vRhoL[i] + ztl * rst);
+        }
+        V.vD[i] = rcp_(soft_w_(fu, zu, su, rzu, rsu, eu) + soft_w_(fl, zl, sl, rzl, rsl, el));
+    } else {
+        V.vD[i] = fu ? su * rzu + eu : su * rzu;
+    }
+}
+// The affine right-hand side of the m x m system from qu = c + R y: (Wu q~u - Wl q~l)/(Wu + Wl), q~ = q + e (z + zt - gamma)
+// (the range role's expression on a row hard on both sides, the elastic role's on a one-sided row)
+template <class T> QPX_DEV T softrange_rhs(const SoftVecs<T>& V, int i, T qu)
+{
+    const T hl = V.vH[i], rhou = V.vRho[i], zu = V.vZ[i];
+    const bool fu = elastic_(rhou);
+    T eu = T(0), qtu = qu;
+    if (fu) {
+        eu = rcp_(rhou + V.vZT[i] * V.vRST[i]);
+        qtu = qu + (zu + V.vZT[i] - V.vGam[i]) * eu;
+    }
+    if (!two_sided_(hl)) return qtu;
+    const T rhol = V.vRhoL[i], zl = V.vZL[i];
+    const bool fl = elastic_(rhol);
+    T el = T(0), qtl = hl - qu;
+    if (fl) {
+        el = rcp_(rhol + V.vZTL[i] * V.vRSTL[i]);
+        qtl = (hl - qu) + (zl + V.vZTL[i] - V.vGamL[i]) * el;
+    }
+    const T wu = soft_w_(fu, zu, V.vS[i], V.vRZ[i], V.vRS[i], eu), wl = soft_w_(fl, zl, V.vSL[i], V.vRZL[i], V.vRSL[i], el);
+    return (wu * qtu - wl * qtl) * V.vD[i];
+}
+// The residuals of the four pairs, mu's sum over the live pairs and the right-hand side of a pass, in the order without the
+// chain wave ahead: the one-sided loop's block for this role, its row loop not unrolled (see softrange_affine_step).  vRH is
+// vB's place: R y of row i is read before the right-hand side of row i is written.
+template <class T, int NS>
+QPX_DEV void softrange_resid_rhs(int lane, int m, T tsz, const SoftVecs<T>& V, const T* vB, const T* vR1, T& pri2, T& szdot)
+{
+#pragma unroll 1
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const T zk = V.vZ[i], sk = V.vS[i], c = V.vC[i], ry = vB[i];
+            const bool fu = elastic_(V.vRho[i]);
+            T rz = sk - c - ry;
+            if (fu) rz -= V.vQT[i];                      // ru = su - c - R y - tu
+            pri2 = fma_(rz, rz, pri2);
+            szdot = fma_(sk, zk, szdot);
+            const T qu = c + ry + tsz * vR1[i];          // affine right-hand side c + R y
+            if (fu) {                                    // rtu = stu - tu
+                const T st = V.vST[i], rt = st - V.vQT[i];
+                pri2 = fma_(rt, rt, pri2);
+                szdot = fma_(st, V.vZT[i], szdot);
+            }
+            const T hl = V.vH[i];
+            if (two_sided_(hl)) {
+                const T sl = V.vSL[i];
+                T rl = sl - (hl - c) + ry;               // rl = sl - cl + R y - tl, rtl = stl - tl
+                if (elastic_(V.vRhoL[i])) {
+                    const T tv = V.vQTL[i], stl = V.vSTL[i], rt = stl - tv;
+                    rl -= tv;
+                    pri2 = fma_(rt, rt, pri2);
+                    szdot = fma_(stl, V.vZTL[i], szdot);
+                }
+                pri2 = fma_(rl, rl, pri2);
+                szdot = fma_(sl, V.vZL[i], szdot);
+            }
+            V.vQUL[i] = qu;
+            V.vRH[i] = softrange_rhs(V, i, qu);
+        }
+    }
+}
+// Start point: w = wt = 1 on the live pairs, vX = v of the system the prologue set up (vRH its right-hand side, vD its
+// diagonal); xu, xl, xtu, xtl are the reference's z_i = -s_i of the augmented QP, shifted as there by the minima over all live
+// entries.  vQT, vQTL take tu, tl for the first pass's residuals.
+template <class T, int NS>
+QPX_DEV void softrange_start_point(const Block& b, int lane, int m, int M8, const SoftVecs<T>& V, T* pSigz, T* pSigs)
+{
+    // (the unshifted xu, xl, xtu, xtl wait in vZ, vZL, vZT, vZTL between the two loops: four register arrays of NS cost the
+    // one-wave four-row form its registers)
+    T mnz = Lim<T>::inf(), mns = Lim<T>::inf();
+#pragma unroll 1
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const T hl = V.vH[i], x = V.vX[i], rhou = V.vRho[i];
+            const bool fu = elastic_(rhou);
+            T xu, xl = T(0), xtu = T(0), xtl = T(0);
+            if (two_sided_(hl)) {
+                const T rhol = V.vRhoL[i];
+                const bool fl = elastic_(rhol);
+                const T c = V.vC[i], rv = -V.vRH[i] - x * V.vD[i];
+                if (fu) {
+                    const T e = rcp_(rhou + T(1));
+                    xu = -rcp_(T(1) + e) * ((c - V.vGam[i] * e) + rv);
+                } else {
+                    xu = -c - rv;
+                }
+                if (fl) {
+                    const T e = rcp_(rhol + T(1));
+                    xl = rcp_(T(1) + e) * (rv - ((hl - c) - V.vGamL[i] * e));
+                    xtl = (V.vGamL[i] - xl) / (rhol + T(1));
+                    mnz = min2_(mnz, xtl);
+                    mns = min2_(mns, -xtl);
+                } else {
+                    xl = rv - (hl - c);
+                }
+                mnz = min2_(mnz, xl);
+                mns = min2_(mns, -xl);
+            } else {
+                xu = x;
+            }
+            if (fu) {
+                xtu = (V.vGam[i] - xu) / (rhou + T(1));
+                mnz = min2_(mnz, xtu);
+                mns = min2_(mns, -xtu);
+            }
+            mnz = min2_(mnz, xu);
+            mns = min2_(mns, -xu);
+            V.vZ[i] = xu; V.vZL[i] = xl; V.vZT[i] = xtu; V.vZTL[i] = xtl;
+        }
+    }
+    mnz = wave_min(b, mnz);
+    mns = wave_min(b, mns);
+    const T sigz = (mnz < T(0)) ? (T(1) - mnz) : T(0);
+    const T sigs = (mns < T(0)) ? (T(1) - mns) : T(0);
+    if (lane == 0) { *pSigz = sigz; *pSigs = sigs; }
+#pragma unroll 1
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const T rhou = V.vRho[i], rhol = V.vRhoL[i];
+            const bool f2 = two_sided_(V.vH[i]), fu = elastic_(rhou), fl = elastic_(rhol);
+            const T xu = V.vZ[i], xl = V.vZL[i], xtu = V.vZT[i], xtl = V.vZTL[i];
+            const T zu = xu + sigz, su = -xu + sigs;
+            const T zl = f2 ? xl + sigz : T(0), sl = f2 ? -xl + sigs : Lim<T>::inf();
+            const T ztu = fu ? xtu + sigz : T(0), stu = fu ? -xtu + sigs : Lim<T>::inf();
+            const T ztl = fl ? xtl + sigz : T(0), stl = fl ? -xtl + sigs : Lim<T>::inf();
+            V.vZ[i] = zu; V.vS[i] = su; V.vZL[i] = zl; V.vSL[i] = sl;
+            V.vZT[i] = ztu; V.vST[i] = stu; V.vZTL[i] = ztl; V.vSTL[i] = stl;
+            V.vBZ[i] = zu; V.vBS[i] = su; V.vBZL[i] = zl; V.vBSL[i] = sl;
+            V.vBZT[i] = ztu; V.vBST[i] = stu; V.vBZTL[i] = ztl; V.vBSTL[i] = stl;
+            V.vA[i] = f2 ? xu - xl : xu;
+            V.vQT[i] = fu ? (xu + xtu - V.vGam[i]) / rhou : T(0);
+            V.vQTL[i] = fl ? (xl + xtl - V.vGamL[i]) / rhol : T(0);
+            softrange_recips(V, f2, fu, fl, i, zu, su, zl, sl, ztu, stu, ztl, stl);
+        } else if (i < M8) {
+            V.vA[i] = T(0);
+        }
+    }
+}
+// Affine step lengths, centring sigma, the corrector's right-hand side.  vX = v of the affine solve, vRH its right-hand side
+// (overwritten by the corrector's), vQUL = qu = c + R y of this pass (overwritten by the lower rows' corrector rs); vQT, vQTL
+// take the t-sides' corrector rs.  The eight directions go to LDS as they are formed, not through registers, and the row loops
+// of this role's blocks are not unrolled: the one-wave four-row form holds its matrix in registers, and four rows' worth of
+// loads in flight spilled 22 of them.
+template <class T, int NS>
+QPX_DEV void softrange_affine_step(const Block& b, int lane, int m, T mu, T szdot, const SoftVecs<T>& V)
+{
+    T t = T(0);
+#pragma unroll 1
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const T hl = V.vH[i], x = V.vX[i], su = V.vS[i], zu = V.vZ[i], rhou = V.vRho[i];
+            const bool fu = elastic_(rhou);
+            T dzu, dsu, dzl = T(0), dsl = T(0), dztu = T(0), dstu = T(0), dztl = T(0), dstl = T(0);
+            T gu = T(0), eu = T(0);              // rho qt of the upper side: zu + ztu - gamma
+            if (fu) {
+                eu = rcp_(rhou + V.vZT[i] * V.vRST[i]);
+                gu = zu + V.vZT[i] - V.vGam[i];
+            }
+            if (two_sided_(hl)) {
+                const T rhol = V.vRhoL[i], sl = V.vSL[i], zl = V.vZL[i];
+                const bool fl = elastic_(rhol);
+                T gl = T(0), el = T(0);
+                if (fl) {
+                    el = rcp_(rhol + V.vZTL[i] * V.vRSTL[i]);
+                    gl = zl + V.vZTL[i] - V.vGamL[i];
+                }
+                const T wu = soft_w_(fu, zu, su, V.vRZ[i], V.vRS[i], eu), wl = soft_w_(fl, zl, sl, V.vRZL[i], V.vRSL[i], el);
+                // qu + R v; the side with the SMALLER W by its formula and the other from v = dzu - dzl (range_affine_step)
+                const T tq = V.vQUL[i] + (-V.vRH[i] - x * V.vD[i]);
+                if (wu >= wl) {
+                    dzl = wl * (fl ? (tq - hl) - gl * el : tq - hl);
+                    dzu = x + dzl;
+                } else {
+                    dzu = -wu * (fu ? tq + gu * eu : tq);
+                    dzl = dzu - x;
+                }
+                dsu = -su - dzu * (su * V.vRZ[i]);
+                dsl = -sl - dzl * (sl * V.vRZL[i]);
+                if (fl) {
+                    const T g = gl + dzl;
+                    dztl = -(V.vZTL[i] * V.vRSTL[i]) * g * el;
+                    dstl = -V.vSTL[i] + g * el;
+                }
+            } else {
+                dzu = x;
+                dsu = -su - x * (su * V.vRZ[i]);
+            }
+            if (fu) {
+                const T g = gu + dzu;
+                dztu = -(V.vZT[i] * V.vRST[i]) * g * eu;
+                dstu = -V.vST[i] + g * eu;
+            }
+            if (dzu < T(0)) t = max2_(t, -dzu * V.vRZ[i]);
+            if (dsu < T(0)) t = max2_(t, -dsu * V.vRS[i]);
+            if (dzl < T(0)) t = max2_(t, -dzl * V.vRZL[i]);
+            if (dsl < T(0)) t = max2_(t, -dsl * V.vRSL[i]);
+            if (dztu < T(0)) t = max2_(t, -dztu * V.vRZT[i]);
+            if (dstu < T(0)) t = max2_(t, -dstu * V.vRST[i]);
+            if (dztl < T(0)) t = max2_(t, -dztl * V.vRZTL[i]);
+            if (dstl < T(0)) t = max2_(t, -dstl * V.vRSTL[i]);
+            V.vDZA[i] = dzu; V.vDSA[i] = dsu; V.vDZAL[i] = dzl; V.vDSAL[i] = dsl;
+            V.vDZAT[i] = dztu; V.vDSAT[i] = dstu; V.vDZATL[i] = dztl; V.vDSATL[i] = dstl;
+        }
+    }
+    t = wave_max(b, t);
+    T al = (t > T(0)) ? T(1) / t : T(1);
+    al = (al < T(1)) ? al : T(1);
+    T t3 = 0;
+#pragma unroll 1
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            t3 = fma_(V.vS[i] + al * V.vDSA[i], V.vZ[i] + al * V.vDZA[i], t3);
+            if (elastic_(V.vRho[i])) t3 = fma_(V.vST[i] + al * V.vDSAT[i], V.vZT[i] + al * V.vDZAT[i], t3);
+            if (two_sided_(V.vH[i])) {
+                t3 = fma_(V.vSL[i] + al * V.vDSAL[i], V.vZL[i] + al * V.vDZAL[i], t3);
+                if (elastic_(V.vRhoL[i])) t3 = fma_(V.vSTL[i] + al * V.vDSATL[i], V.vZTL[i] + al * V.vDZATL[i], t3);
+            }
+        }
+    }
+    t3 = wave_sum(b, t3);
+    T sig = t3 / szdot;
+    sig = sig * sig * sig;
+#pragma unroll 1
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const bool f2 = two_sided_(V.vH[i]), fu = elastic_(V.vRho[i]), fl = elastic_(V.vRhoL[i]);
+            const T rsu = (-mu * sig + V.vDSA[i] * V.vDZA[i]) * V.vRS[i];
+            const T rsl = f2 ? (-mu * sig + V.vDSAL[i] * V.vDZAL[i]) * V.vRSL[i] : T(0);
+            const T rstu = fu ? (-mu * sig + V.vDSAT[i] * V.vDZAT[i]) * V.vRST[i] : T(0);
+            const T rstl = fl ? (-mu * sig + V.vDSATL[i] * V.vDZATL[i]) * V.vRSTL[i] : T(0);
+            V.vRSC[i] = rsu;
+            V.vQUL[i] = rsl;
+            V.vQT[i] = rstu;
+            V.vQTL[i] = rstl;
+            // (e and W of each soft side once more: held through the two reductions they cost registers, not time)
+            const T du = V.vS[i] * V.vRZ[i];
+            const T eu = soft_e_(fu, V.vRho[i], V.vZT[i], V.vRST[i]);
+            if (f2) {
+                // W q~ of each side: rs on a hard side (W = w, q~ = rs/w)
+                const T dl = V.vSL[i] * V.vRZL[i];
+                const T el = soft_e_(fl, V.vRhoL[i], V.vZTL[i], V.vRSTL[i]);
+                const T pu = fu ? rcp_(du + eu) * (rsu * du - rstu * eu) : rsu;
+                const T pl = fl ? rcp_(dl + el) * (rsl * dl - rstl * el) : rsl;
+                V.vRH[i] = (pu - pl) * V.vD[i];
+            } else {
+                V.vRH[i] = rsu * du - (fu ? rstu * eu : T(0));
+            }
+        }
+    }
+}
+// The combined step with the 0.999 damping, tau, z' (zu - zl on a two-sided row), tu, tl of the new iterate (vQT, vQTL), and
+// the next pass's reciprocals and diagonal.  The combined directions replace the affine ones in LDS.
+template <class T, int NS>
+QPX_DEV void softrange_final_step(const Block& b, int lane, int m, const SoftVecs<T>& V, T* pTau, T* pAlphaPrev, T sigz)
+{
+    T t = T(0);
+#pragma unroll 1
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const T x = V.vX[i], su = V.vS[i], zu = V.vZ[i], rhou = V.vRho[i], rsu = V.vRSC[i];
+            const bool fu = elastic_(rhou);
+            const T eu = soft_e_(fu, rhou, V.vZT[i], V.vRST[i]);
+            T cu, cl = T(0), dzl = T(0), dsl = T(0), dztu = T(0), dstu = T(0), dztl = T(0), dstl = T(0);
+            if (two_sided_(V.vH[i])) {
+                const T rhol = V.vRhoL[i], sl = V.vSL[i], zl = V.vZL[i], rsl = V.vQUL[i];
+                const bool fl = elastic_(rhol);
+                const T el = soft_e_(fl, rhol, V.vZTL[i], V.vRSTL[i]);
+                const T wu = soft_w_(fu, zu, su, V.vRZ[i], V.vRS[i], eu), wl = soft_w_(fl, zl, sl, V.vRZL[i], V.vRSL[i], el);
+                const T rv = -V.vRH[i] - x * V.vD[i];
+                if (wu >= wl) {                  // the corrector's dz: the smaller W's side by its formula, as in the affine step
+                    cl = fl ? wl * (rv - (rsl * (sl * V.vRZL[i]) - V.vQTL[i] * el)) : wl * rv - rsl;
+                    cu = x + cl;
+                } else {
+                    cu = fu ? -wu * ((rsu * (su * V.vRZ[i]) - V.vQT[i] * eu) + rv) : -rsu - wu * rv;
+                    cl = cu - x;
+                }
+                dzl = V.vDZAL[i] + cl;
+                dsl = V.vDSAL[i] + (-rsl - cl) * (sl * V.vRZL[i]);
+                if (fl) {
+                    const T rst = V.vQTL[i];
+                    dztl = V.vDZATL[i] - (rhol * rst + (V.vZTL[i] * V.vRSTL[i]) * cl) * el;
+                    dstl = V.vDSATL[i] - (rst - cl) * el;
+                }
+            } else {
+                cu = x;
+            }
+            const T dzu = V.vDZA[i] + cu;
+            const T dsu = V.vDSA[i] + (-rsu - cu) * (su * V.vRZ[i]);
+            if (fu) {
+                const T rst = V.vQT[i];
+                dztu = V.vDZAT[i] - (rhou * rst + (V.vZT[i] * V.vRST[i]) * cu) * eu;
+                dstu = V.vDSAT[i] - (rst - cu) * eu;
+            }
+            if (dzu < T(0)) t = max2_(t, -dzu * V.vRZ[i]);
+            if (dsu < T(0)) t = max2_(t, -dsu * V.vRS[i]);
+            if (dzl < T(0)) t = max2_(t, -dzl * V.vRZL[i]);
+            if (dsl < T(0)) t = max2_(t, -dsl * V.vRSL[i]);
+            if (dztu < T(0)) t = max2_(t, -dztu * V.vRZT[i]);
+            if (dstu < T(0)) t = max2_(t, -dstu * V.vRST[i]);
+            if (dztl < T(0)) t = max2_(t, -dztl * V.vRZTL[i]);
+            if (dstl < T(0)) t = max2_(t, -dstl * V.vRSTL[i]);
+            V.vDZA[i] = dzu; V.vDSA[i] = dsu; V.vDZAL[i] = dzl; V.vDSAL[i] = dsl;
+            V.vDZAT[i] = dztu; V.vDSAT[i] = dstu; V.vDZATL[i] = dztl; V.vDSATL[i] = dstl;
+        }
+    }
+    t = wave_max(b, t);
+    T al = (t > T(0)) ? T(1) / t : T(1);
+    al = T(0.999) * al;
+    al = (al < T(1)) ? al : T(1);
+    const T tau = (T(1) - al) * *pTau;
+    const T tsz = tau * sigz;
+    b.wave_sync();           // every lane has read the old tau
+    if (lane == 0) { *pTau = tau; *pAlphaPrev = al; }
+#pragma unroll 1
+    for (int k = 0; k < NS; ++k) {
+        const int i = k * kWave + lane;
+        if (i < m) {
+            const T rhou = V.vRho[i], rhol = V.vRhoL[i];
+            const bool f2 = two_sided_(V.vH[i]), fu = elastic_(rhou), fl = elastic_(rhol);
+            const T zu = fma_(al, V.vDZA[i], V.vZ[i]), su = fma_(al, V.vDSA[i], V.vS[i]);
+            V.vZ[i] = zu; V.vS[i] = su;
+            T zl = T(0), sl = Lim<T>::inf(), ztu = T(0), stu = Lim<T>::inf(), ztl = T(0), stl = Lim<T>::inf(), tu = T(0), tl = T(0);
+            if (f2) {
+                zl = fma_(al, V.vDZAL[i], V.vZL[i]);
+                sl = fma_(al, V.vDSAL[i], V.vSL[i]);
+                V.vZL[i] = zl; V.vSL[i] = sl;
+            }
+            if (fu) {
+                ztu = fma_(al, V.vDZAT[i], V.vZT[i]);
+                stu = fma_(al, V.vDSAT[i], V.vST[i]);
+                V.vZT[i] = ztu; V.vST[i] = stu;
+                tu = ((zu - tsz) + (ztu - tsz) - V.vGam[i]) / rhou;
+            }
+            if (fl) {
+                ztl = fma_(al, V.vDZATL[i], V.vZTL[i]);
+                stl = fma_(al, V.vDSATL[i], V.vSTL[i]);
+                V.vZTL[i] = ztl; V.vSTL[i] = stl;
+                tl = ((zl - tsz) + (ztl - tsz) - V.vGamL[i]) / rhol;
+            }
+            V.vQT[i] = tu;
+            V.vQTL[i] = tl;
+            V.vA[i] = f2 ? (zu - zl) : (zu - tsz);          // (vA is vDZA's place: read above, in this lane)
+            softrange_recips(V, f2, fu, fl, i, zu, su, zl, sl, ztu, stu, ztl, stl);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // The PDIPM loop on the format-3 blob.  Mathematics and control flow: see ipm_body (same
 // reference citations); the factorisation is ldl_inv and every solve is two triangular mat-vecs.
 // kRole 1, kRange: the form's range role (qpx_forms.h: kIpmRangeRole) -- two-sided rows, the range_* blocks above; kRole 2,
-// kElastic: its elastic role (kIpmElasticRole) -- the elastic_* blocks.  The one-sided forms compile none of either, and a
-// role none of the other.
+// kElastic: its elastic role (kIpmElasticRole) -- the elastic_* blocks; kRole 3, kSoft: its soft-range role (kIpmSoftRangeRole)
+// -- the softrange_* blocks.  The one-sided forms compile none of these, and a role none of another's.
 template <class T, class Mat, int NS, int kRole, class P>
 QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, const P& g)
 {
-    constexpr bool kRange = kRole == 1, kElastic = kRole == 2;
+    constexpr bool kRange = kRole == 1, kElastic = kRole == 2, kSoft = kRole == 3;
     constexpr int M8 = Mat::MP, NT = Mat::NT;
     const int n = a.n, m = a.m, q = a.q;
     const FacLayout lay = fac_layout(n, m, q, a.images);
@@ -1370,10 +1779,19 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     // elastic role: t's side -- z, s, their reciprocals, best iterate and affine step in the range role's places; vQT (in
     // vQUL's) is t from the block that forms an iterate to the next pass's residuals and t's side's corrector rs from the affine
     // step to the combined one; vGam, vRho are gamma and rho (+inf: a hard row) -- one vector more than the range role
-    T *vZT = vZL, *vST = vSL, *vRZT = vRZL, *vRST = vRSL, *vBZT = vBZL, *vBST = vBSL, *vDZAT = vDZAL, *vDSAT = vDSAL, *vQT = vQUL;
-    T* vGam = vH;
+    // soft-range role: the range role's vectors as they are, then tu's side (8), tl's side (8), vQT / vQTL (tu / tl, then each
+    // side's corrector rs, as vQT of the elastic role) and the four penalty vectors -- 49 vectors
+    T* vZT = kSoft ? vH + v : vZL;
+    T *vST = vZT + v, *vRZT = vST + v, *vRST = vRZT + v, *vBZT = vRST + v, *vBST = vBZT + v, *vDZAT = vBST + v, *vDSAT = vDZAT + v;
+    T* vZTL = vDSAT + v;
+    T *vSTL = vZTL + v, *vRZTL = vSTL + v, *vRSTL = vRZTL + v, *vBZTL = vRSTL + v, *vBSTL = vBZTL + v, *vDZATL = vBSTL + v, *vDSATL = vDZATL + v;
+    T* vQT = kSoft ? vDSATL + v : vQUL;
+    T* vQTL = vQT + v;
+    T* vGam = kSoft ? vQTL + v : vH;
     T* vRho = vGam + v;
-    T* sc = kElastic ? vRho + v : (kRange ? vH + v : vX0 + v);              // 16 scalars of the IPM state
+    T* vGamL = vRho + v;
+    T* vRhoL = vGamL + v;
+    T* sc = kSoft ? vRhoL + v : (kElastic ? vRho + v : (kRange ? vH + v : vX0 + v));              // 16 scalars of the IPM state
     int* ctrl = reinterpret_cast<int*>(sc + 16);    // 8 elements of control words
     T* scr = sc + 24;     // Mat::scratch_elems()
 
@@ -1383,33 +1801,52 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     const int io32 = a.io32;
     const In<T> pg(a.p, (size_t)qp * a.sp, io32), hg(a.h, (size_t)qp * a.sh, io32);
     const In<T> bg(q > 0 ? a.b : nullptr, (size_t)qp * a.sb, io32);
-    const In<T> lwg(kRange ? a.lower : nullptr, (size_t)qp * a.slo, io32);
+    const In<T> lwg(kRange || kSoft ? a.lower : nullptr, (size_t)qp * a.slo, io32);
 
     // range role: a lower bound that is NaN, +inf or not below its h -- every wave looks at all of them, so the decision is uniform
     bool bad_lower = false;
-    if constexpr (kRange) {
+    if constexpr (kRange || kSoft) {
         for (int i = b.lane(); i < m; i += kWave)
             if (!(lwg[i] < hg[i])) bad_lower = true;
         bad_lower = b.any(bad_lower);
     }
     // elastic role: a gamma that is NaN or negative, a rho that is NaN or not positive -- decided in the same way
-    const In<T> gmg(kElastic ? a.gamma : nullptr, (size_t)qp * a.sgamma, io32), rhg(kElastic ? a.rho : nullptr, (size_t)qp * a.srho, io32);
-    if constexpr (kElastic) {
+    const In<T> gmg(kElastic || kSoft ? a.gamma : nullptr, (size_t)qp * a.sgamma, io32), rhg(kElastic || kSoft ? a.rho : nullptr, (size_t)qp * a.srho, io32);
+    if constexpr (kElastic || kSoft) {
         for (int i = b.lane(); i < m; i += kWave)
             if (!(gmg[i] >= T(0)) || !(rhg[i] > T(0))) bad_lower = true;
         bad_lower = b.any(bad_lower);
     }
+    // soft-range role: the lower side's penalty, on every row
+    const In<T> gmlg(kSoft ? a.gamma_lo : nullptr, (size_t)qp * a.sgamma_lo, io32), rhlg(kSoft ? a.rho_lo : nullptr, (size_t)qp * a.srho_lo, io32);
+    if constexpr (kSoft) {
+        for (int i = b.lane(); i < m; i += kWave)
+            if (!(gmlg[i] >= T(0)) || !(rhlg[i] > T(0))) bad_lower = true;
+        bad_lower = b.any(bad_lower);
+    }
+    SoftVecs<T> V;            // (soft-range role only: the blocks' view of the vectors)
+    if constexpr (kSoft)
+        V = SoftVecs<T>{vH, vC, vD, vA, vX, vRH, vRSC, vQUL, vZ, vS, vRZ, vRS, vBZ, vBS, vDZA, vDSA, vZL, vSL, vRZL, vRSL, vBZL, vBSL, vDZAL, vDSAL,
+                        vZT, vST, vRZT, vRST, vBZT, vBST, vDZAT, vDSAT, vZTL, vSTL, vRZTL, vRSTL, vBZTL, vBSTL, vDZATL, vDSATL, vQT, vQTL,
+                        vGam, vRho, vGamL, vRhoL};
     if ((a.status[qp] & (QPX_ST_Q_NOT_SPD | QPX_ST_A_RANK)) || bad_lower) {
         const T nanv = Lim<T>::inf() - Lim<T>::inf();
         for (int i = b.tid; i < n; i += b.nt) put_(a.zhat, io32, (size_t)qp * n + i, nanv);
         for (int i = b.tid; i < m; i += b.nt) {
             put_(a.lam, io32, (size_t)qp * m + i, nanv);
             put_(a.slack, io32, (size_t)qp * m + i, nanv);
-            if constexpr (kRange || kElastic) {
+            if constexpr (kRange || kElastic || kSoft) {
                 put_(a.lam_lo, io32, (size_t)qp * m + i, nanv);
                 put_(a.slack_lo, io32, (size_t)qp * m + i, nanv);
             }
-            if constexpr (kElastic) put_(a.tviol, io32, (size_t)qp * m + i, nanv);
+            if constexpr (kElastic || kSoft) put_(a.tviol, io32, (size_t)qp * m + i, nanv);
+            if constexpr (kSoft) {
+                put_(a.lam_t, io32, (size_t)qp * m + i, nanv);
+                put_(a.slack_t, io32, (size_t)qp * m + i, nanv);
+                put_(a.lam_tl, io32, (size_t)qp * m + i, nanv);
+                put_(a.slack_tl, io32, (size_t)qp * m + i, nanv);
+                put_(a.tviol_lo, io32, (size_t)qp * m + i, nanv);
+            }
         }
         for (int i = b.tid; i < q; i += b.nt) put_(a.nu, io32, (size_t)qp * q + i, nanv);
         if (b.tid == 0) {
@@ -1466,7 +1903,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         // || G^T 1 ||: read from the blob once, not once per iteration (a global load on the chain).  Range role: || G^T e ||,
         // e = 1 on the one-sided rows, from the caller -- the blob's scalar is that number only when no row is two-sided
         // (elastic role: || G'^T 1 || of the augmented QP, from the caller as well)
-        if constexpr (kRange || kElastic) sc[kGt1] = a.gt1 ? In<T>(a.gt1, (size_t)qp, io32)[0] : T(0);
+        if constexpr (kRole != 0) sc[kGt1] = a.gt1 ? In<T>(a.gt1, (size_t)qp, io32)[0] : T(0);
         else sc[kGt1] = F[lay.scal];
         ctrl[kStop] = 0; ctrl[kNnot] = 0; ctrl[kFloor] = 0; ctrl[kSt] = 0; ctrl[kIters] = 0;
     }
@@ -1510,11 +1947,65 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
             vZT[i] = T(1); vST[i] = T(1); vRZT[i] = T(1); vRST[i] = T(1);
             vDZAT[i] = T(0); vDSAT[i] = T(0); vQT[i] = T(0);
         }
+        if constexpr (kSoft) {
+            // the start point's system with w = wt = 1 on every live pair: e = 1/(rho + 1) and W = 1/(1 + e) on a soft side, e = 0
+            // and W = 1 on a hard one; q~u = c - gamma_u eu, q~l = (h - l) - c - gamma_l el.  Two-sided row: diagonal 1/(Wu + Wl),
+            // right-hand side (Wu q~u - Wl q~l)/(Wu + Wl), e = 0 for R e (the range role's 1/2 (cu - cl) when both sides are hard);
+            // one-sided row: the elastic role's 1 + eu and q~u.  A side is soft where its gamma and rho are both finite.
+            T hl = Lim<T>::inf(), rh = T(0), dd = T(1), e = T(1);
+            T gu = T(0), ru = Lim<T>::inf(), gl = T(0), rl = Lim<T>::inf();
+            if (i < m) {
+                const T c = vC[i], g0 = gmg[i], r0 = rhg[i];
+                const bool fu = g0 < Lim<T>::inf() && r0 < Lim<T>::inf();
+                T eu = T(0);
+                hl = hg[i] - lwg[i];
+                if (fu) { eu = rcp_(r0 + T(1)); gu = g0; ru = r0; }
+                if (two_sided_(hl)) {
+                    const T g1 = gmlg[i], r1 = rhlg[i];
+                    const bool fl = g1 < Lim<T>::inf() && r1 < Lim<T>::inf();
+                    T el = T(0);
+                    if (fl) { el = rcp_(r1 + T(1)); gl = g1; rl = r1; }
+                    if (!fu && !fl) {
+                        rh = T(0.5) * (c - (hl - c));
+                        dd = T(0.5);
+                    } else {
+                        const T wu = fu ? rcp_(T(1) + eu) : T(1), wl = fl ? rcp_(T(1) + el) : T(1);
+                        dd = rcp_(wu + wl);
+                        rh = (wu * (c - gu * eu) - wl * ((hl - c) - gl * el)) * dd;
+                    }
+                    e = T(0);
+                } else {
+                    rh = c;
+                    if (fu) {
+                        rh -= g0 * eu;
+                        dd = T(1) + eu;
+                    }
+                }
+            }
+            vH[i] = hl; vRH[i] = rh; vD[i] = dd; vA[i] = e;
+            vGam[i] = gu; vRho[i] = ru; vGamL[i] = gl; vRhoL[i] = rl;
+            vZL[i] = T(1); vSL[i] = T(1); vRZL[i] = T(1); vRSL[i] = T(1);
+            vZT[i] = T(1); vST[i] = T(1); vRZT[i] = T(1); vRST[i] = T(1);
+            vZTL[i] = T(1); vSTL[i] = T(1); vRZTL[i] = T(1); vRSTL[i] = T(1);
+            vDZAL[i] = T(0); vDSAL[i] = T(0); vDZAT[i] = T(0); vDSAT[i] = T(0); vDZATL[i] = T(0); vDSATL[i] = T(0);
+            vQUL[i] = T(0); vQT[i] = T(0); vQTL[i] = T(0);
+        }
     }
     if constexpr (kRange) {
         if (w0) {            // m' = m + the two-sided rows: the live rows of the doubled QP
             T cnt = T(0);
             for (int i = lane; i < m; i += kWave) cnt += two_sided_(hg[i] - lwg[i]) ? T(1) : T(0);
+            cnt = wave_sum(b, cnt);
+            if (lane == 0) sc[kMp] = mT + cnt;
+        }
+    }
+    if constexpr (kSoft) {
+        if (w0) {            // m' = the live pairs: m + the two-sided rows + the soft sides
+            T cnt = T(0);
+            for (int i = lane; i < m; i += kWave) {
+                cnt += (gmg[i] < Lim<T>::inf() && rhg[i] < Lim<T>::inf()) ? T(1) : T(0);
+                if (two_sided_(hg[i] - lwg[i])) cnt += (gmlg[i] < Lim<T>::inf() && rhlg[i] < Lim<T>::inf()) ? T(2) : T(1);
+            }
             cnt = wave_sum(b, cnt);
             if (lane == 0) sc[kMp] = mT + cnt;
         }
@@ -1531,7 +2022,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     // and nu = nu0 - W^T z are dual- and equality-feasible by construction, so pass -1 (the start point: one factorisation and
     // one solve) is not needed and the passes begin at 0.  R 1 is formed in pass -1 only: zeroed, tau sigma_z R 1 must not
     // meet what LDS held.  The best iterate is taken at pass 0 as ever; it is set here for a breakdown inside that pass.
-    const bool warm = !kElastic && a.lam0 && ctrl[kWarm];
+    const bool warm = !kElastic && !kSoft && a.lam0 && ctrl[kWarm];
     if (warm) {
         const T fl = a.warm_floor;
         for (int i = b.tid; i < M8; i += NT) {
@@ -1549,7 +2040,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     if (b.tid == 0 && a.warm_used) a.warm_used[qp] = warm;
     const int it0 = warm ? 0 : -1;
     Mat::sync(b);
-    if constexpr (kRange || kElastic) mT = sc[kMp];
+    if constexpr (kRole != 0) mT = sc[kMp];
 
     // ---- pass -1 is the start point: T = R + I, z_i = -T^-1 c, s_i = -z_i, shifts (batch.py:61-87),
     // and R 1 on the way; passes 0.. are the IPM iterations.  One loop so that the factorisation and
@@ -1585,6 +2076,12 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                             if (two_sided_(vH[i])) szdot = fma_(vSL[i], vZL[i], szdot);
                         } else if constexpr (kElastic) {      // (... elastic_recips)
                             if (elastic_(vRho[i])) szdot = fma_(vST[i], vZT[i], szdot);
+                        } else if constexpr (kSoft) {         // (... softrange_recips)
+                            if (elastic_(vRho[i])) szdot = fma_(vST[i], vZT[i], szdot);
+                            if (two_sided_(vH[i])) {
+                                szdot = fma_(vSL[i], vZL[i], szdot);
+                                if (elastic_(vRhoL[i])) szdot = fma_(vSTL[i], vZTL[i], szdot);
+                            }
                         } else {
                             const T rzk = rcp_(zk);
                             vRZ[i] = rzk;
@@ -1612,7 +2109,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 const int i = k * kWave + lane;
                 if (i < m) {
                     T rz = vS[i] - vC[i] - vB[i];
-                    if constexpr (kElastic) {            // ru = su - c - R zu' - t, rt = st - t
+                    if constexpr (kElastic || kSoft) {   // ru = su - c - R zu' - t, rt = st - t (kSoft: R y, tu, stu)
                         if (elastic_(vRho[i])) {
                             const T tv = vQT[i], rt = vST[i] - tv;
                             rz -= tv;
@@ -1620,10 +2117,17 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                         }
                     }
                     pri2 = fma_(rz, rz, pri2);
-                    if constexpr (kRange) {
+                    if constexpr (kRange || kSoft) {
                         const T hl = vH[i];
                         if (two_sided_(hl)) {
-                            const T rl = vSL[i] - (hl - vC[i]) + vB[i];
+                            T rl = vSL[i] - (hl - vC[i]) + vB[i];
+                            if constexpr (kSoft) {       // rl = sl - cl + R y - tl, rtl = stl - tl
+                                if (elastic_(vRhoL[i])) {
+                                    const T tv = vQTL[i], rt = vSTL[i] - tv;
+                                    rl -= tv;
+                                    pri2 = fma_(rt, rt, pri2);
+                                }
+                            }
                             pri2 = fma_(rl, rl, pri2);
                         }
                     }
@@ -1644,7 +2148,8 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 bres = resid; nnot = 0;
                 for (int i = lane; i < m; i += kWave) {
                     vBZ[i] = vZ[i]; vBS[i] = vS[i];
-                    if constexpr (kRange || kElastic) { vBZL[i] = vZL[i]; vBSL[i] = vSL[i]; }
+                    if constexpr (kRange || kElastic || kSoft) { vBZL[i] = vZL[i]; vBSL[i] = vSL[i]; }
+                    if constexpr (kSoft) { vBZT[i] = vZT[i]; vBST[i] = vST[i]; vBZTL[i] = vZTL[i]; vBSTL[i] = vSTL[i]; }
                 }
             } else if (a.stall_policy == 1 || (a.stall_policy == 2 && mT * mu < feas)) {
                 nnot += 1;
@@ -1686,6 +2191,9 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                         // (c + R zu) + e (zu + zt - gamma), e = 1/(rho + wt); a hard row keeps qu
                         const T rho = vRho[i];
                         vRH[i] = elastic_(rho) ? qu + (vZ[i] + vZT[i] - vGam[i]) * rcp_(rho + vZT[i] * vRST[i]) : qu;
+                    } else if constexpr (kSoft) {
+                        vQUL[i] = qu;
+                        vRH[i] = softrange_rhs(V, i, qu);
                     } else {
                         vRH[i] = qu;
                     }
@@ -1706,6 +2214,14 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                         if constexpr (kElastic) {
                             if (i < m) { const bool f = elastic_(vRho[i]); vBZT[i] = f ? T(1) : T(0); vBST[i] = f ? T(1) : Lim<T>::inf(); }
                         }
+                        if constexpr (kSoft) {
+                            if (i < m) {
+                                const bool f2 = two_sided_(vH[i]), fu = elastic_(vRho[i]), fl = elastic_(vRhoL[i]);
+                                vBZL[i] = f2 ? T(1) : T(0); vBSL[i] = f2 ? T(1) : Lim<T>::inf();
+                                vBZT[i] = fu ? T(1) : T(0); vBST[i] = fu ? T(1) : Lim<T>::inf();
+                                vBZTL[i] = fl ? T(1) : T(0); vBSTL[i] = fl ? T(1) : Lim<T>::inf();
+                            }
+                        }
                         vA[i] = T(0);
                     }
                 }
@@ -1721,6 +2237,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                                                                vBZ, vBS, vBZL, vBSL, sc + kSigz, sc + kSigs);
                 else if constexpr (kElastic) elastic_start_point<T, NS>(b, lane, m, M8, vX, vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT, vRST, vD,
                                                                         vA, vBZ, vBS, vBZT, vBST, vQT, sc + kSigz, sc + kSigs);
+                else if constexpr (kSoft) softrange_start_point<T, NS>(b, lane, m, M8, V, sc + kSigz, sc + kSigs);
                 else ipm_start_point<T, NS>(b, lane, m, M8, vX, vZ, vS, vA, vBZ, vBS, sc + kSigz, sc + kSigs);
             }
             Mat::sync(b);
@@ -1732,6 +2249,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                                                            vRH, vQUL, vRSC, vDZA, vDSA, vDZAL, vDSAL);
             else if constexpr (kElastic) elastic_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT,
                                                                     vRST, vX, vRH, vQT, vRSC, vDZA, vDSA, vDZAT, vDSAT);
+            else if constexpr (kSoft) softrange_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], V);
             else ipm_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vZ, vS, vRZ, vRS, vD, vX, vRSC, vRH, vDZA, vDSA);
         }
         Mat::sync(b);
@@ -1747,6 +2265,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                                                           vDSA, vDZAL, vDSAL, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
             else if constexpr (kElastic) elastic_final_step<T, NS>(b, lane, m, vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT, vRST, vD, vX, vRSC,
                                                                    vQT, vDZA, vDSA, vDZAT, vDSAT, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
+            else if constexpr (kSoft) softrange_final_step<T, NS>(b, lane, m, V, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
             else ipm_final_step<T, NS>(b, lane, m, vZ, vS, vRZ, vRS, vD, vX, vRSC, vDZA, vDSA, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
         }
         Mat::sync(b);
@@ -1762,6 +2281,9 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
         if (w0 && !first) {
             const T tsz = sc[kTau] * sc[kSigz];
             T pri2 = 0, szdot = 0;
+            if constexpr (kSoft) {
+                softrange_resid_rhs<T, NS>(lane, m, tsz, V, vB, vR1, pri2, szdot);
+            } else {
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
                 const int i = k * kWave + lane;
@@ -1809,6 +2331,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                     }
                 }
             }
+            }
             pri2 = wave_sum(b, pri2);
             szdot = wave_sum(b, szdot);
             const T mu = abs_(szdot / mT);
@@ -1826,7 +2349,8 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 bres = resid; nnot = 0;
                 for (int i = lane; i < m; i += kWave) {
                     vBZ[i] = vZ[i]; vBS[i] = vS[i];
-                    if constexpr (kRange || kElastic) { vBZL[i] = vZL[i]; vBSL[i] = vSL[i]; }
+                    if constexpr (kRange || kElastic || kSoft) { vBZL[i] = vZL[i]; vBSL[i] = vSL[i]; }
+                    if constexpr (kSoft) { vBZT[i] = vZT[i]; vBST[i] = vST[i]; vBZTL[i] = vZTL[i]; vBSTL[i] = vSTL[i]; }
                 }
             } else if (a.stall_policy == 1 || (a.stall_policy == 2 && mT * mu < feas)) {
                 nnot += 1;
@@ -1872,6 +2396,14 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                         if constexpr (kElastic) {
                             if (i < m) { const bool f = elastic_(vRho[i]); vBZT[i] = f ? T(1) : T(0); vBST[i] = f ? T(1) : Lim<T>::inf(); }
                         }
+                        if constexpr (kSoft) {
+                            if (i < m) {
+                                const bool f2 = two_sided_(vH[i]), fu = elastic_(vRho[i]), fl = elastic_(vRhoL[i]);
+                                vBZL[i] = f2 ? T(1) : T(0); vBSL[i] = f2 ? T(1) : Lim<T>::inf();
+                                vBZT[i] = fu ? T(1) : T(0); vBST[i] = fu ? T(1) : Lim<T>::inf();
+                                vBZTL[i] = fl ? T(1) : T(0); vBSTL[i] = fl ? T(1) : Lim<T>::inf();
+                            }
+                        }
                         vA[i] = T(0);
                     }
                 }
@@ -1888,6 +2420,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                                                                vBZ, vBS, vBZL, vBSL, sc + kSigz, sc + kSigs);
                 else if constexpr (kElastic) elastic_start_point<T, NS>(b, lane, m, M8, vX, vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT, vRST, vD,
                                                                         vA, vBZ, vBS, vBZT, vBST, vQT, sc + kSigz, sc + kSigs);
+                else if constexpr (kSoft) softrange_start_point<T, NS>(b, lane, m, M8, V, sc + kSigz, sc + kSigs);
                 else ipm_start_point<T, NS>(b, lane, m, M8, vX, vZ, vS, vA, vBZ, vBS, sc + kSigz, sc + kSigs);
             }
             Mat::sync(b);
@@ -1899,6 +2432,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                                                            vRH, vQUL, vRSC, vDZA, vDSA, vDZAL, vDSAL);
             else if constexpr (kElastic) elastic_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT,
                                                                     vRST, vX, vRH, vQT, vRSC, vDZA, vDSA, vDZAT, vDSAT);
+            else if constexpr (kSoft) softrange_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], V);
             else ipm_affine_step<T, NS>(b, lane, m, sc[kMu], sc[kSzdot], vZ, vS, vRZ, vRS, vD, vX, vRSC, vRH, vDZA, vDSA);
         }
         Mat::sync(b);
@@ -1910,6 +2444,7 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                                                           vDSA, vDZAL, vDSAL, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
             else if constexpr (kElastic) elastic_final_step<T, NS>(b, lane, m, vGam, vRho, vZ, vS, vZT, vST, vRZ, vRS, vRZT, vRST, vD, vX, vRSC,
                                                                    vQT, vDZA, vDSA, vDZAT, vDSAT, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
+            else if constexpr (kSoft) softrange_final_step<T, NS>(b, lane, m, V, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
             else ipm_final_step<T, NS>(b, lane, m, vZ, vS, vRZ, vRS, vD, vX, vRSC, vDZA, vDSA, vA, sc + kTau, sc + kAlphaPrev, sc[kSigz]);
         }
         Mat::sync(b);
@@ -1933,6 +2468,17 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 const T bzl = vBZL[i];
                 put_(a.lam_lo, io32, (size_t)qp * m + i, bzl);
                 put_(a.slack_lo, io32, (size_t)qp * m + i, vBSL[i]);
+                vA[i] = two_sided_(vH[i]) ? bz - bzl : bz - bts;
+            } else if constexpr (kSoft) {
+                const T bzl = vBZL[i], bzt = vBZT[i], bztl = vBZTL[i], rhou = vRho[i], rhol = vRhoL[i];
+                put_(a.lam_lo, io32, (size_t)qp * m + i, bzl);
+                put_(a.slack_lo, io32, (size_t)qp * m + i, vBSL[i]);
+                put_(a.lam_t, io32, (size_t)qp * m + i, bzt);
+                put_(a.slack_t, io32, (size_t)qp * m + i, vBST[i]);
+                put_(a.lam_tl, io32, (size_t)qp * m + i, bztl);
+                put_(a.slack_tl, io32, (size_t)qp * m + i, vBSTL[i]);
+                put_(a.tviol, io32, (size_t)qp * m + i, elastic_(rhou) ? ((bz - bts) + (bzt - bts) - vGam[i]) / rhou : T(0));
+                put_(a.tviol_lo, io32, (size_t)qp * m + i, elastic_(rhol) ? ((bzl - bts) + (bztl - bts) - vGamL[i]) / rhol : T(0));
                 vA[i] = two_sided_(vH[i]) ? bz - bzl : bz - bts;
             } else if constexpr (kElastic) {
                 const T bzt = vBZT[i], rho = vRho[i];
@@ -1989,11 +2535,12 @@ QPX_DEV void ipm_loop_body(const Block& b, const IpmArgs<T>& a, int qp, T* lds)
 }
 
 // (NBL >= kIpmRangeRole: the range role of the form with NBL - kIpmRangeRole blocks, >= kIpmElasticRole: its elastic role,
-// qpx_forms.h)
+// >= kIpmSoftRangeRole: its soft-range role, qpx_forms.h)
 template <class T, int GS, int NBL, int NS>
 QPX_DEV void ipm_grid_body(const Block& b, const IpmArgs<T>& a, int qp, T* lds)
 {
-    if constexpr (NBL >= kIpmElasticRole) ipm_loop_body<T, GridMat<T, GS, NBL - kIpmElasticRole>, NS, 2>(b, a, qp, lds);
+    if constexpr (NBL >= kIpmSoftRangeRole) ipm_loop_body<T, GridMat<T, GS, NBL - kIpmSoftRangeRole>, NS, 3>(b, a, qp, lds);
+    else if constexpr (NBL >= kIpmElasticRole) ipm_loop_body<T, GridMat<T, GS, NBL - kIpmElasticRole>, NS, 2>(b, a, qp, lds);
     else if constexpr (NBL >= kIpmRangeRole) ipm_loop_body<T, GridMat<T, GS, NBL - kIpmRangeRole>, NS, 1>(b, a, qp, lds);
     else ipm_loop_body<T, GridMat<T, GS, NBL>, NS>(b, a, qp, lds);
 }

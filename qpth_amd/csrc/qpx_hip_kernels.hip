@@ -93,6 +93,9 @@ QPX_FORMS_IPM_RANGE_GRID(QPX_INSTR)
 // (NBL + kIpmElasticRole: its elastic role, qpx_ipm_elastic)
 #define QPX_INSTE(NBL, NS) template int launch_ipm_grid<double, NBL + kIpmElasticRole, NS>(const IpmArgs<double>&, size_t, void*);
 QPX_FORMS_IPM_RANGE_GRID(QPX_INSTE)
+// (NBL + kIpmSoftRangeRole: its soft-range role, qpx_ipm_soft_range)
+#define QPX_INSTS(NBL, NS) template int launch_ipm_grid<double, NBL + kIpmSoftRangeRole, NS>(const IpmArgs<double>&, size_t, void*);
+QPX_FORMS_IPM_RANGE_GRID(QPX_INSTS)
 #endif
 #elif QPX_TU_KERNEL == 7
 // (NBL >= kKktMultiRole: the form's multi-right-hand-side role, >= kKktB2Role: its second-order role, qpx_forms.h)
@@ -246,6 +249,8 @@ QPX_FORMS_IPM_TILE(QPX_INSTT)
 QPX_FORMS_IPM_RANGE_TILE(QPX_INSTTR)
 #define QPX_INSTTE(NBL, NW, NS, CH) template int launch_ipm_tile<NBL + kIpmElasticRole, NW, NS, CH>(const IpmArgs<double>&, size_t, void*);
 QPX_FORMS_IPM_RANGE_TILE(QPX_INSTTE)
+#define QPX_INSTTS(NBL, NW, NS, CH) template int launch_ipm_tile<NBL + kIpmSoftRangeRole, NW, NS, CH>(const IpmArgs<double>&, size_t, void*);
+QPX_FORMS_IPM_RANGE_TILE(QPX_INSTTS)
 #endif
 #endif
 

@@ -183,6 +183,12 @@ template <class T> struct IpmArgs {
     const T *gamma = nullptr, *rho = nullptr;
     long long sgamma = 0, srho = 0;
     T* tviol = nullptr;
+    // soft two-sided rows (qpx_ipm_soft_range; the forms of kIpmSoftRangeRole only): lower, gamma, rho above (the upper side's
+    // penalty), gamma_lo, rho_lo (B,m) the lower side's, batch strides sgamma_lo, srho_lo; lam_lo, slack_lo above: the lower
+    // rows'; lam_t, slack_t, tviol / lam_tl, slack_tl, tviol_lo (B,m): multipliers, slacks and values of tu >= 0 / tl >= 0
+    const T *gamma_lo = nullptr, *rho_lo = nullptr;
+    long long sgamma_lo = 0, srho_lo = 0;
+    T *lam_t = nullptr, *slack_t = nullptr, *lam_tl = nullptr, *slack_tl = nullptr, *tviol_lo = nullptr;
 };
 
 template <class T> struct KktArgs {

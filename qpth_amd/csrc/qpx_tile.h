@@ -1358,8 +1358,9 @@ template <int NBL, int NW, int NS, bool CH = false>
 QPX_DEV void ipm_tile_body(const Block& b, const IpmArgs<double>& a, int qp, double* lds)
 {
     // (NBL >= kIpmRangeRole: the range role of the form with NBL - kIpmRangeRole tile rows, >= kIpmElasticRole: its elastic role,
-    // qpx_forms.h)
-    if constexpr (NBL >= kIpmElasticRole) ipm_loop_body<double, TileMat<NBL - kIpmElasticRole, NW, CH>, NS, 2>(b, a, qp, lds);
+    // >= kIpmSoftRangeRole: its soft-range role, qpx_forms.h)
+    if constexpr (NBL >= kIpmSoftRangeRole) ipm_loop_body<double, TileMat<NBL - kIpmSoftRangeRole, NW, CH>, NS, 3>(b, a, qp, lds);
+    else if constexpr (NBL >= kIpmElasticRole) ipm_loop_body<double, TileMat<NBL - kIpmElasticRole, NW, CH>, NS, 2>(b, a, qp, lds);
     else if constexpr (NBL >= kIpmRangeRole) ipm_loop_body<double, TileMat<NBL - kIpmRangeRole, NW, CH>, NS, 1>(b, a, qp, lds);
     else ipm_loop_body<double, TileMat<NBL, NW, CH>, NS>(b, a, qp, lds);
 }

@@ -36,7 +36,8 @@ class IpmResult:
     __slots__ = ("zhat", "nu", "lam", "slacks", "iters", "status", "best_resid", "trace", "_warm_used",
                  "centre_resid", "centre_steps",         # these two: set by KKTFactors.centre only
                  "lam_lo", "slacks_lo",                  # ... these by KKTFactors.ipm_range only
-                 "lam_t", "slacks_t", "t")               # ... and these by KKTFactors.ipm_elastic only
+                 "lam_t", "slacks_t", "t",               # ... these by KKTFactors.ipm_elastic and ipm_soft_range
+                 "lam_tl", "slacks_tl", "t_lo")          # ... and these by KKTFactors.ipm_soft_range only
 
     @property
     def warm_used(self):
@@ -146,6 +147,46 @@ def as_l1(l1, Q, nineq, nBatch=1):
     if l1.dim() > 2 or (l1.dim() >= 1 and l1.size(-1) != nineq) or (l1.dim() == 2 and nBatch > 1 and l1.size(0) != nBatch):
         raise ValueError("qpth_amd: l1 has shape %s; expected (nBatch, %d), (%d,) or ()" % (tuple(l1.shape), nineq, nineq))
     return l1
+
+
+class SoftRange:
+    """The bounds and penalties of SOFT two-sided rows, the value of QPFunction(...)(..., soft_range=):
+          min 1/2 z'Qz + p'z + sum_i ( l1_i tu_i + 1/2 rho_i tu_i^2 + l1_lower_i tl_i + 1/2 rho_lower_i tl_i^2 )
+          s.t.  lower - tl <= Gz <= h + tu,  tu, tl >= 0,  Az = b.
+    Each field is a tensor of shape (nBatch, nineq), (nineq,) (shared by the batch) or () (one for every row), or a Python
+    float; l1_lower and rho_lower default to the upper side's l1 and rho.  lower = -inf makes a row one-sided; l1 = +inf or
+    rho = +inf on a side makes that side hard.  Immutable; the tensors among the five fields that require grad are
+    differentiable inputs of the call."""
+    __slots__ = ("lower", "l1", "rho", "l1_lower", "rho_lower")
+
+    def __init__(self, lower, l1, rho, l1_lower=None, rho_lower=None):
+        for name, val in (("lower", lower), ("l1", l1), ("rho", rho), ("l1_lower", l1 if l1_lower is None else l1_lower),
+                          ("rho_lower", rho if rho_lower is None else rho_lower)):
+            if val is None:
+                raise ValueError("qpth_amd: SoftRange needs %s" % name)
+            object.__setattr__(self, name, val)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("SoftRange is immutable")
+
+    def __repr__(self):
+        return "SoftRange(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+
+    def fields(self, Q, nineq, nBatch=1):
+        """the five fields as tensors of Q's dtype and device (a number -> a 0-dim tensor), shapes checked as as_rho does;
+        the VALUES are checked by the loop kernel"""
+        out = []
+        for name in self.__slots__:
+            x = getattr(self, name)
+            if not torch.is_tensor(x):
+                x = torch.tensor(float(x), dtype=Q.dtype, device=Q.device)
+            if x.dtype != Q.dtype or x.device != Q.device:
+                raise ValueError("qpth_amd: soft_range.%s is %s on %s, the QP is %s on %s" % (name, x.dtype, x.device, Q.dtype, Q.device))
+            if x.dim() > 2 or (x.dim() >= 1 and x.size(-1) != nineq) or (x.dim() == 2 and nBatch > 1 and x.size(0) != nBatch):
+                raise ValueError("qpth_amd: soft_range.%s has shape %s; expected (nBatch, %d), (%d,) or ()"
+                                 % (name, tuple(x.shape), nineq, nineq))
+            out.append(x)
+        return out
 
 
 class _PinnedPool:
@@ -684,6 +725,126 @@ a non-zero diagonal.
         lc, sc = lam.clamp(min=1e-8), slacks.clamp(min=1e-8)
         dt = lam_t.clamp(min=1e-8) / slacks_t.clamp(min=1e-8)
         return sc + lc / (rho + dt), dt
+
+    # -- soft two-sided rows lower - tl <= G z <= h + tu --------------------------------
+    def soft_range_ok(self):
+        """does qpx_ipm_soft_range serve these factors (under the knob they were built with)?  float64 tensors, the thread-grid /
+        tile kernels' sizes (nz+neq+nineq <= 208), HARD factors"""
+        if self.soft or self.wide or self.dtype != torch.float64 or not hasattr(self.lib.dll, "qpx_soft_range_supported"):
+            return False
+        with self._knob():
+            return bool(self.lib.dll.qpx_soft_range_supported(_lib.QPX_F64, self.n, self.m, self.q))
+
+    def _soft_range_refusal(self):
+        return ValueError("qpth_amd: soft two-sided rows (soft_range) are served for float64 tensors up to nz + neq + nineq = 208 "
+                          "under the default knob, on hard factors; got %s, nz = %d, nineq = %d, neq = %d%s.  Write the augmented "
+                          "dense QP in (z, tu, tl) instead" % (str(self.dtype).replace("torch.", ""), self.n, self.m, self.q,
+                                                               ", soft rows" if self.soft else ""))
+
+    def gt1_soft_range(self, h, lower, gamma_u, rho_u, gamma_l, rho_l):
+        """sqrt(|| G^T e ||^2 + 4 (k_u + k_l)) per QP: e = 1 on the one-sided rows, k the soft sides (gamma and rho finite; a
+        lower side on a two-sided row only) -- the augmented QP's || G'^T 1 || of the stop rule.  torch operations, no host sync."""
+        g = self.gt1_of(lower, h)
+        two = ~torch.isinf(h - lower)
+        k = (torch.isfinite(gamma_u) & torch.isfinite(rho_u)).to(self.dtype) \
+            + (two & torch.isfinite(gamma_l) & torch.isfinite(rho_l)).to(self.dtype)
+        k = k.sum(-1).reshape(-1).expand(self.B)
+        return torch.sqrt(g.square() + 4.0 * k).contiguous()
+
+    def ipm_soft_range(self, p, h, lower, l1, rho, l1_lower, rho_lower, b, eps=1e-12, maxIter=20, notImprovedLim=3,
+                       stall_policy=None, want_trace=False):
+        """The IPM loop for  lower - tl <= G z <= h + tu, tu, tl >= 0  with the penalty  l1 t + 1/2 rho t^2  of each side in nineq
+        rows (qpx_ipm_soft_range): the iterates of ipm() on the augmented QP in (z, tu, tl), one launch, no host sync.  The five
+        vectors are (B, nineq), (1, nineq) or (nineq,).  The result has lam, slacks (upper rows), lam_lo, slacks_lo (lower rows),
+        lam_t, slacks_t, t (tu >= 0) and lam_tl, slacks_tl, t_lo (tl >= 0); an absent side reads 0, +inf and 0.  A bad entry
+        (NaN, lower not below h, l1 < 0, rho <= 0): QPX_ST_NONFINITE in `status` (raise_on_failure)."""
+        if not self.soft_range_ok():
+            raise self._soft_range_refusal()
+        B, n, m, q = self.B, self.n, self.m, self.q
+        dt, dev = self.dtype, self.device
+        self._check(p, n, "p")
+        self._check(h, m, "h")
+        names = ("lower", "l1", "rho", "l1_lower", "rho_lower")
+        vecs = [x.detach() for x in (lower, l1, rho, l1_lower, rho_lower)]
+        for x, name in zip(vecs, names):
+            self._check(x, m, name)
+        lower, l1, rho, l1_lower, rho_lower = vecs
+        if q:
+            if b is None or b.nelement() == 0:
+                raise RuntimeError("qpth_amd: A has %d rows but b is empty" % q)
+            self._check(b, q, "b")
+        r = IpmResult()
+        r.zhat = torch.empty(B, n, dtype=dt, device=dev)
+        r.nu = torch.empty(B, q, dtype=dt, device=dev)
+        for name in ("lam", "slacks", "lam_lo", "slacks_lo", "lam_t", "slacks_t", "lam_tl", "slacks_tl", "t", "t_lo"):
+            setattr(r, name, torch.empty(B, m, dtype=dt, device=dev))
+        r.iters = torch.empty(B, dtype=torch.int32, device=dev)
+        r.best_resid = torch.empty(B, dtype=dt, device=dev)
+        r.trace = torch.full((maxIter, B, 3), float('nan'), dtype=dt, device=dev) if want_trace else None
+        # the status words of THIS launch, and what raise_on_failure reads, copied to pinned memory in front of the loop
+        # launch: as ipm_range does
+        r.status = self.status.clone()
+        r._warm_used = None
+
+        def word(bad):
+            return bad.any(-1).reshape(-1).expand(B).to(torch.int32)
+
+        hd = h.detach()
+        words = torch.stack((self.status, word(~(lower < hd)), word(~(l1 >= 0)), word(~(rho > 0)), word(~(l1_lower >= 0)),
+                             word(~(rho_lower > 0))))
+        msgs = ("lower must be below h", "l1 must be non-negative", "rho must be positive", "l1_lower must be non-negative",
+                "rho_lower must be positive")
+        if words.is_cuda and not torch.cuda.is_current_stream_capturing():
+            host = torch.empty(words.shape, dtype=torch.int32, pin_memory=True)
+            host.copy_(words, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            self._range = (host, ev, msgs)
+        else:
+            self._range = (words, None, msgs)
+        if stall_policy is None:
+            stall_policy = default_stall_policy(B)
+        gt1 = self.gt1_soft_range(hd, lower, l1, rho, l1_lower, rho_lower)
+        with self._knob():
+            self.lib.ipm_soft_range(B, n, m, q, p, h, lower, l1, rho, l1_lower, rho_lower, gt1, b if q else None, self.blob,
+                                    self.sfac, eps, maxIter, notImprovedLim, stall_policy, r.zhat, r.nu if q else None, r.lam,
+                                    r.slacks, r.lam_lo, r.slacks_lo, r.lam_t, r.slacks_t, r.lam_tl, r.slacks_tl, r.t, r.t_lo,
+                                    r.iters, r.status, r.best_resid, r.trace)
+        return r
+
+    def backward_soft_range(self, res, rho, rho_lower, dl_dz, want=(True,) * 11, shared=(False,) * 6):
+        """Gradients (dQ, dp, dG, dh, dA, db, dlower, dl1, drho, dl1_lower, drho_lower) of a loss on zhat at the solution `res`
+        of ipm_soft_range; rho, rho_lower (B, nineq) with +inf on every hard side (either of the side's penalties +inf).  No
+        kernel of its own: qpx_backward_range on the same factors with the effective slack of each side (elastic_eff), so
+        that its d is 1/e_u + 1/e_l, e = 1/d_side + 1/(rho + dt), and the true lam - lam_lo meets dx in dG.  From its dz = v
+        the sides' shares give dh = -v_u, dlower = v_l (v_u = v (1/e_u)/d, v_l = -v (1/e_l)/d) and, per side,
+        dl1 = v_side/(dt + rho), drho = t dl1: exactly 0 on a hard or absent side.  `shared` reduces the six parameters as
+        backward() does; the five others come back per QP, (B, nineq), for the caller to reduce."""
+        want = [bool(w) for w in want]
+        pen = any(want[6:])
+        seff_u, dtu = self.elastic_eff(res.lam, res.slacks, res.lam_t, res.slacks_t, rho)
+        seff_l, dtl = self.elastic_eff(res.lam_lo, res.slacks_lo, res.lam_tl, res.slacks_tl, rho_lower)
+        w7 = tuple(want[:3]) + (want[3] or pen,) + tuple(want[4:6]) + (pen,)
+        sh = tuple(shared[:3]) + (shared[3] and not pen,) + tuple(shared[4:6]) + (False,)
+        dQ, dp, dG, dh, dA, db, dlo = self.backward_range(res.zhat, res.lam, seff_u, res.lam_lo, seff_l, res.nu, dl_dz,
+                                                          want=w7, shared=sh)
+        out = [None] * 5
+        if pen:
+            if want[6]:
+                out[0] = dlo
+            if want[7] or want[8]:
+                g = -dh / (dtu + rho)
+                out[1] = g if want[7] else None
+                out[2] = g * res.t if want[8] else None
+            if want[9] or want[10]:
+                g = dlo / (dtl + rho_lower)
+                out[3] = g if want[9] else None
+                out[4] = g * res.t_lo if want[10] else None
+            if not want[3]:
+                dh = None
+            elif shared[3]:
+                dh = dh.mean(0)
+        return (dQ, dp, dG, dh, dA, db) + tuple(out)
 
     # -- factor_kkt + solve_kkt (batch.py:435-470, 349-372) ----------------------------------
     def solve_kkt(self, d, rx, rs, rz, ry, refine=0):

@@ -22,6 +22,10 @@ in l as well: the loop's and the backward's range role, the same number of launc
 QPFunction(...)(Q, p, G, h, A, b, rho, l1=gamma) makes the rows ELASTIC: the exact penalty gamma't + 1/2 t'diag(rho)t on the violations
 t >= 0 of Gz <= h + t, in nineq rows and nz variables -- not the augmented dense QP in (z, t) --, differentiable in gamma and rho:
 the loop's elastic role on the hard QP's factors, the backward as it stands (qpx_ipm_elastic).
+QPFunction(...)(Q, p, G, h, A, b, soft_range=SoftRange(lower, l1, rho)) composes the two: l - tl <= Gz <= h + tu with a penalty on
+each side's violation, every row choosing its own kind, in nineq rows and nz variables -- not the augmented dense QP in (z, tu, tl)
+with 4 nineq rows --, differentiable in the five fields: the loop's soft-range role, the range role's backward (qpx_ipm_soft_range,
+DESIGN 4.13).
 """
 from enum import Enum
 
@@ -30,7 +34,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .kkt import KKTFactors, as_kappa, as_l1, as_lower, as_rho
+from .kkt import KKTFactors, SoftRange, as_kappa, as_l1, as_lower, as_rho
 from .solvers.pdipm import batch as pdipm_b
 from .util import expandParam, extract_nBatch
 
@@ -64,8 +68,23 @@ def f64_arithmetic_serves(nz, nineq, neq, lib=None):
 def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                maxIter=20, solver=QPSolvers.PDIPM_BATCHED,
                check_Q_spd=True, refine=None, duals=False, warm_start=None, kappa_tol=1e-9, kappa_steps=20):
-    """Returns f(Q, p, G, h, A, b, rho=None, kappa=None, lower=None, l1=None).  `refine`, `duals`, `warm_start` and the inputs `rho`,
-    `kappa`, `lower` and `l1` are what the reference does not have.
+    """Returns f(Q, p, G, h, A, b, rho=None, kappa=None, lower=None, l1=None, soft_range=None).  `refine`, `duals`, `warm_start` and the
+    inputs `rho`, `kappa`, `lower`, `l1` and `soft_range` are what the reference does not have.
+    soft_range: SOFT two-sided inequality rows, a qpth_amd.SoftRange(lower, l1, rho, l1_lower=None, rho_lower=None),
+          min 1/2 z'Qz + p'z + sum_i ( l1_i tu_i + 1/2 rho_i tu_i^2 + l1_lower_i tl_i + 1/2 rho_lower_i tl_i^2 )
+          s.t.  lower - tl <= Gz <= h + tu,  tu, tl >= 0,  Az = b:
+      boxes, ranges and trust regions that may be violated at a price.  Each row decides its kind: lower_i = -inf makes it
+      one-sided, l1 = +inf or rho = +inf on a side makes that side hard, so one call mixes hard, two-sided, elastic and
+      soft two-sided rows.  The iterates, iteration counts and solution of the reference on the augmented QP in (z, tu, tl) --
+      nz + 2 nineq variables, 4 nineq rows --, whose Newton system collapses to the nineq x nineq system the loop factors anyway,
+      on the HARD QP's factors.  The fields: tensors of shape (nBatch, nineq), (nineq,) or (), or floats; lower < h strictly on
+      every two-sided row, l1 >= 0, rho > 0 (the pure l1 penalty is not served); a bad entry raises ValueError from the
+      forward.  Returns zhat; reverse mode gives gradients to the six parameters and to those of the five fields that are tensors
+      requiring grad (un-batched ones reduced as l1 and rho are), exactly 0 on an absent or hard side.  float64 inputs at
+      sizes the thread-grid / tile kernels serve (nz+neq+nineq <= 208) only; not together with rho, kappa, lower or l1 (the
+      holder carries them), duals=True, warm_start, refine > 0, float32 inputs or an external solver: each a ValueError that
+      names the augmented dense QP as the way out.  Forward mode and second derivatives: RuntimeError.  soft_range=None is the
+      call as before: the same nodes and launches.
     l1: elastic inequality rows, together with rho,
           min 1/2 z'Qz + p'z + sum_i ( l1_i t_i + 1/2 rho_i t_i^2 )   s.t.  Gz <= h + t,  t >= 0,  Az = b,
       the EXACT penalty with a quadratic tail: where the hard QP is feasible and l1_i exceeds its multipliers the solution is the
@@ -560,6 +579,94 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                 grads = grads[:4] + (None, None)
             return grads + (drho, dl1)
 
+    class QPSoftRangeFunctionFn(Function):
+        """the node of soft two-sided rows: lower, l1, rho, l1_lower, rho_lower behind the six parameters.  Forward:
+        the hard QP's factors and the loop's soft-range role; backward: the range role's launch on the same factors with the
+        effective slack of each side (KKTFactors.backward_soft_range)."""
+        @staticmethod
+        def forward(ctx, Q_, p_, G_, h_, A_, b_, *fields_):
+            nBatch = extract_nBatch(Q_, p_, G_, h_, A_, b_)
+            for X in fields_:
+                if X.dim() == 2:
+                    nBatch = max(nBatch, X.size(0))
+            nineq = G_.size(-2)
+            Q, _ = expandParam(Q_, nBatch, 3)
+            p, _ = expandParam(p_, nBatch, 2)
+            G, _ = expandParam(G_, nBatch, 3)
+            h, _ = expandParam(h_, nBatch, 2)
+            A, _ = expandParam(A_, nBatch, 3)
+            b, _ = expandParam(b_, nBatch, 2)
+            ctx.neq = A_.size(-2) if A_.nelement() > 0 else 0
+            lo, gu, ru, gl, rl = [X.detach().expand(nineq).unsqueeze(0) if X.dim() < 2 else X.detach() for X in fields_]
+            fac = KKTFactors.build(Q, G, A, nBatch)
+            res = fac.ipm_soft_range(p, h, lo, gu, ru, gl, rl, b, eps, maxIter, notImprovedLim, want_trace=(verbose == 1))
+            # one small read-back: the reference raises here too (qp.py:81-85), and so does a bad entry of the five fields
+            fac.raise_on_failure(check_Q_spd)
+            if verbose == 1:
+                _print_trace(res)
+            if verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
+                print(pdipm_b.INACC_ERR)
+            ctx.fac, ctx.res = fac, res
+            # a side is hard where either of its penalties is +inf (the kernel's rule): rho = +inf there for the derivatives
+            inf = torch.full((nBatch, nineq), float("inf"), dtype=Q.dtype, device=Q.device)
+            ctx.rho_u = torch.where(torch.isfinite(gu), ru, inf)
+            ctx.rho_l = torch.where(torch.isfinite(gl), rl, inf)
+            ctx.dims = [X.dim() for X in fields_]
+            ctx.save_for_backward(Q_, p_, G_, h_, A_, b_)
+            return res.zhat
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            raise RuntimeError("qpth_amd: forward mode is not served with soft two-sided rows (soft_range); write the augmented "
+                               "dense QP in (z, tu, tl)")
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dl_dzhat):
+            Q, p, G, h, A, b = ctx.saved_tensors
+            shared = (Q.dim() == 2, p.dim() == 1, G.dim() == 2, h.dim() == 1, A.dim() == 2, b.dim() == 1)
+            grads = ctx.fac.backward_soft_range(ctx.res, ctx.rho_u, ctx.rho_l, dl_dzhat, want=tuple(ctx.needs_input_grad[:11]),
+                                                shared=shared)
+            six, five = grads[:6], []
+            # an un-batched field: `.mean(0)`, a scalar summed over the rows as well (as l1 and rho of the elastic rows)
+            for g, dim in zip(grads[6:], ctx.dims):
+                if g is not None and dim < 2:
+                    g = g.mean(0)
+                    g = g.sum() if dim == 0 else g
+                five.append(g)
+            if ctx.neq == 0:
+                six = six[:4] + (None, None)
+            return six + tuple(five)
+
+    def _apply_soft_range(Q, p, G, h, A, b, rho, kappa, lower, l1, soft_range):
+        what = "qpth_amd: soft_range (soft two-sided rows)"
+        out = "; write the augmented dense QP in (z, tu, tl) instead"
+        if not isinstance(soft_range, SoftRange):
+            raise ValueError(what + " must be a qpth_amd.SoftRange(lower, l1, rho, l1_lower=None, rho_lower=None), got %s"
+                             % type(soft_range).__name__)
+        for name, val in (("rho", rho), ("kappa", kappa), ("lower", lower), ("l1", l1)):
+            if val is not None:
+                raise ValueError(what + " together with %s is not served: the SoftRange holder carries the bounds and penalties" % name
+                                 + out)
+        if duals:
+            raise ValueError(what + " with duals=True is not served (the multipliers are no outputs of this node)" + out)
+        if warm_start is not None:
+            raise ValueError(what + " with warm_start is not served" + out)
+        if refine is not None and int(refine) > 0:
+            raise ValueError(what + " with refine=%d is not served: pass refine=0 or refine=None" % int(refine) + out)
+        if solver != QPSolvers.PDIPM_BATCHED:
+            raise ValueError(what + " is served by solver=QPSolvers.PDIPM_BATCHED only" + out)
+        if Q.dtype != torch.float64:
+            raise ValueError(what + " is served for float64 inputs only (the soft-range role exists in float64 arithmetic), got %s"
+                             % Q.dtype + out)
+        nineq, nz = G.size(-2), G.size(-1)
+        neq = A.size(-2) if A.nelement() > 0 else 0
+        if not _lib.backend_for(Q).dll.qpx_soft_range_supported(_lib.QPX_F64, nz, nineq, neq):
+            raise ValueError(what + " is served up to nz + neq + nineq = 208 (the thread-grid / tile kernels, "
+                             "qpx_soft_range_supported); got nz = %d, nineq = %d, neq = %d" % (nz, nineq, neq) + out)
+        fields = soft_range.fields(Q, nineq, extract_nBatch(Q, p, G, h, A, b))
+        return QPSoftRangeFunctionFn.apply(Q, p, G, h, A, b, *fields)
+
     def _apply_elastic(Q, p, G, h, A, b, rho, kappa, lower, l1):
         what = "qpth_amd: l1 (elastic rows)"
         out = "; write the augmented dense QP in (z, t) instead"
@@ -635,7 +742,9 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         kappa = as_kappa(kappa, Q, nineq, extract_nBatch(Q, p, G, h, A, b))
         return QPSmoothFunctionFn.apply(Q, p, G, h, A, b, kappa, loop_eps)
 
-    def apply(Q, p, G, h, A, b, rho=None, kappa=None, lower=None, l1=None):
+    def apply(Q, p, G, h, A, b, rho=None, kappa=None, lower=None, l1=None, soft_range=None):
+        if soft_range is not None:
+            return _apply_soft_range(Q, p, G, h, A, b, rho, kappa, lower, l1, soft_range)
         if l1 is not None:
             return _apply_elastic(Q, p, G, h, A, b, rho, kappa, lower, l1)
         if lower is not None:
