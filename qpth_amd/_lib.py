@@ -175,23 +175,28 @@ class QpxLib:
             _ptr(factors), _ptr(status), _stream(factors)))
 
     # -- batch.py:47-207 ----------------------------------------------------------------
+    def _ipm_call(self, fn, common, *more, wide=False):
+        """one loop entry point `fn`: qpx_ipm's arguments -- every loop entry point begins with them; `common`, in the order
+        unpacked below --, then `more` (what the entry point takes behind them, marshalled by the caller), then the stream"""
+        (B, n, m, q, p, h, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
+         zhat, nu, lam, slack, iters, status, best_resid, trace) = common
+        pp, hp, bp = Param(p, 2), Param(h, 2), Param(b, 2)
+        self.check(fn(
+            _code(factors, wide), B, n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
+            _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
+            _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid),
+            _ptr(trace), *more, _stream(factors)))
+
     def ipm(self, B, n, m, q, p, h, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
             zhat, nu, lam, slack, iters, status, best_resid, trace=None, wide=False,
             lam0=None, s0=None, warm_floor=1e-2, warm_used=None):
         """lam0, s0 (B,m) dense: the warm start (qpx_ipm_warm); without them the call is qpx_ipm itself, as before."""
-        pp, hp, bp = Param(p, 2), Param(h, 2), Param(b, 2)
+        common = (B, n, m, q, p, h, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
+                  zhat, nu, lam, slack, iters, status, best_resid, trace)
         if lam0 is not None or s0 is not None:
-            self.check(self.dll.qpx_ipm_warm(
-                _code(factors, wide), B, n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
-                _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
-                _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid),
-                _ptr(trace), _ptr(lam0), _ptr(s0), float(warm_floor), _ptr(warm_used), _stream(factors)))
+            self._ipm_call(self.dll.qpx_ipm_warm, common, _ptr(lam0), _ptr(s0), float(warm_floor), _ptr(warm_used), wide=wide)
             return
-        self.check(self.dll.qpx_ipm(
-            _code(factors, wide), B, n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
-            _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
-            _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid),
-            _ptr(trace), _stream(factors)))
+        self._ipm_call(self.dll.qpx_ipm, common, wide=wide)
 
     # -- qp.py:92-96 ---------------------------------------------------------------------
     def forward(self, B, n, m, q, Q, p, G, h, A, b, factors, eps, maxIter, notImprovedLim,
@@ -244,12 +249,11 @@ class QpxLib:
     def ipm_range(self, B, n, m, q, p, h, lower, gt1, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
                   zhat, nu, lam, slack, lam_lo, slack_lo, iters, status, best_resid, trace=None):
         """lower (B,m), (1,m) or (m,) (shared: batch stride 0), -inf = a one-sided row; gt1 (B,) = || G^T e || or None (0)"""
-        pp, hp, bp, lp = Param(p, 2), Param(h, 2), Param(b, 2), Param(lower, 2)
-        self.check(self.dll.qpx_ipm_range(
-            _dtype_code(factors), B, n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
-            _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
-            _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid), _ptr(trace),
-            lp.ptr, lp.stride, _ptr(gt1), _ptr(lam_lo), _ptr(slack_lo), _stream(factors)))
+        lp = Param(lower, 2)
+        common = (B, n, m, q, p, h, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
+                  zhat, nu, lam, slack, iters, status, best_resid, trace)
+        self._ipm_call(self.dll.qpx_ipm_range, common,
+                       lp.ptr, lp.stride, _ptr(gt1), _ptr(lam_lo), _ptr(slack_lo))
 
     def backward_range(self, B, n, m, q, factors, sfac, zhat, lam, slack, lam_lo, slack_lo, nu, dl_dz, dQ, dp, dG, dA, db,
                        status, dx=None, dz=None, dy=None):
@@ -263,12 +267,11 @@ class QpxLib:
     def ipm_elastic(self, B, n, m, q, p, h, gamma, rho, gt1, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
                     zhat, nu, lam, slack, lam_t, slack_t, t, iters, status, best_resid, trace=None):
         """gamma, rho (B,m), (1,m) or (m,) (shared: batch stride 0), +inf in either = a hard row; gt1 (B,) = || G'^T 1 ||"""
-        pp, hp, bp, gp, rp = Param(p, 2), Param(h, 2), Param(b, 2), Param(gamma, 2), Param(rho, 2)
-        self.check(self.dll.qpx_ipm_elastic(
-            _dtype_code(factors), B, n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
-            _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
-            _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid), _ptr(trace),
-            gp.ptr, gp.stride, rp.ptr, rp.stride, _ptr(gt1), _ptr(lam_t), _ptr(slack_t), _ptr(t), _stream(factors)))
+        gp, rp = Param(gamma, 2), Param(rho, 2)
+        common = (B, n, m, q, p, h, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
+                  zhat, nu, lam, slack, iters, status, best_resid, trace)
+        self._ipm_call(self.dll.qpx_ipm_elastic, common,
+                       gp.ptr, gp.stride, rp.ptr, rp.stride, _ptr(gt1), _ptr(lam_t), _ptr(slack_t), _ptr(t))
 
     # -- soft two-sided rows lower - tl <= G z <= h + tu (DESIGN 4.13): the loop's soft-range role, float64
     def ipm_soft_range(self, B, n, m, q, p, h, lower, gamma_u, rho_u, gamma_l, rho_l, gt1, b, factors, sfac, eps, maxIter,
@@ -276,15 +279,12 @@ class QpxLib:
                        t, t_lo, iters, status, best_resid, trace=None):
         """lower and the four penalty vectors (B,m), (1,m) or (m,) (shared: batch stride 0); -inf in lower = a one-sided row,
         +inf in a side's gamma or rho = a hard side; gt1 (B,) = || G'^T 1 ||"""
-        pp, hp, bp, lp = Param(p, 2), Param(h, 2), Param(b, 2), Param(lower, 2)
-        gu, ru, gl, rl = Param(gamma_u, 2), Param(rho_u, 2), Param(gamma_l, 2), Param(rho_l, 2)
-        self.check(self.dll.qpx_ipm_soft_range(
-            _dtype_code(factors), B, n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
-            _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
-            _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid), _ptr(trace),
-            lp.ptr, lp.stride, gu.ptr, gu.stride, ru.ptr, ru.stride, gl.ptr, gl.stride, rl.ptr, rl.stride, _ptr(gt1),
-            _ptr(lam_lo), _ptr(slack_lo), _ptr(lam_t), _ptr(slack_t), _ptr(lam_tl), _ptr(slack_tl), _ptr(t), _ptr(t_lo),
-            _stream(factors)))
+        lp, gu, ru, gl, rl = Param(lower, 2), Param(gamma_u, 2), Param(rho_u, 2), Param(gamma_l, 2), Param(rho_l, 2)
+        common = (B, n, m, q, p, h, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
+                  zhat, nu, lam, slack, iters, status, best_resid, trace)
+        self._ipm_call(self.dll.qpx_ipm_soft_range, common,
+                       lp.ptr, lp.stride, gu.ptr, gu.stride, ru.ptr, ru.stride, gl.ptr, gl.stride, rl.ptr, rl.stride, _ptr(gt1),
+                       _ptr(lam_lo), _ptr(slack_lo), _ptr(lam_t), _ptr(slack_t), _ptr(lam_tl), _ptr(slack_tl), _ptr(t), _ptr(t_lo))
 
     # -- forward mode (QPFunctionFn.jvp): the tangent of the solution, one KKT solve with the backward's matrix
     def jvp(self, B, n, m, q, factors, sfac, zhat, lam, slack, nu, tQ, tp, tG, th, tA, tb, dzhat, status,

@@ -96,57 +96,65 @@ def _is_shared(X, B):
     return X.dim() == 2 or X.stride(0) == 0 or (B > 1 and X.size(0) == 1)
 
 
+def _row_param(x, name, Q, nineq, nBatch, scalar_ok=True):
+    """A per-row parameter as every entry point takes it: a tensor of Q's dtype and device, shape (nBatch, nineq), (nineq,) or
+    -- scalar_ok -- (), or then a Python number (-> a 0-dim tensor).  Raises ValueError, naming it `name`, otherwise."""
+    shapes = "(nBatch, %d), (%d,) or ()" % (nineq, nineq) if scalar_ok else "(nBatch, %d) or (%d,)" % (nineq, nineq)
+    if not torch.is_tensor(x):
+        if not scalar_ok:
+            raise ValueError("qpth_amd: %s must be a tensor of shape %s" % (name, shapes))
+        x = torch.tensor(float(x), dtype=Q.dtype, device=Q.device)
+    if x.dtype != Q.dtype or x.device != Q.device:
+        raise ValueError("qpth_amd: %s is %s on %s, the QP is %s on %s" % (name, x.dtype, x.device, Q.dtype, Q.device))
+    if (x.dim() > 2 or (x.dim() == 0 and not scalar_ok) or (x.dim() >= 1 and x.size(-1) != nineq)
+            or (x.dim() == 2 and nBatch > 1 and x.size(0) != nBatch)):
+        raise ValueError("qpth_amd: %s has shape %s; expected %s" % (name, tuple(x.shape), shapes))
+    return x
+
+
 def as_rho(rho, Q, nineq, nBatch=1):
     """The penalties of the soft rows as every entry point takes them: a tensor of Q's dtype and device, shape
     (nBatch, nineq), (nineq,) or (), or a Python number (-> a 0-dim tensor).  Raises ValueError otherwise; the VALUES
     (> 0, +inf = a hard row) are checked by the pre-factorisation kernel (KKTFactors.raise_on_failure)."""
-    if not torch.is_tensor(rho):
-        rho = torch.tensor(float(rho), dtype=Q.dtype, device=Q.device)
-    if rho.dtype != Q.dtype or rho.device != Q.device:
-        raise ValueError("qpth_amd: rho is %s on %s, the QP is %s on %s" % (rho.dtype, rho.device, Q.dtype, Q.device))
-    if rho.dim() > 2 or (rho.dim() >= 1 and rho.size(-1) != nineq) or (rho.dim() == 2 and nBatch > 1 and rho.size(0) != nBatch):
-        raise ValueError("qpth_amd: rho has shape %s; expected (nBatch, %d), (%d,) or ()" % (tuple(rho.shape), nineq, nineq))
-    return rho
+    return _row_param(rho, "rho", Q, nineq, nBatch)
 
 
 def as_kappa(kappa, Q, nineq, nBatch=1):
     """The barrier weights of the smoothed QP as every entry point takes them, as as_rho: a tensor of Q's dtype
     and device, shape (nBatch, nineq), (nineq,) or (), or a Python number (-> a 0-dim tensor).  Raises ValueError otherwise;
     the VALUES (finite, > 0) are checked by the centring kernel."""
-    if not torch.is_tensor(kappa):
-        kappa = torch.tensor(float(kappa), dtype=Q.dtype, device=Q.device)
-    if kappa.dtype != Q.dtype or kappa.device != Q.device:
-        raise ValueError("qpth_amd: kappa is %s on %s, the QP is %s on %s" % (kappa.dtype, kappa.device, Q.dtype, Q.device))
-    if (kappa.dim() > 2 or (kappa.dim() >= 1 and kappa.size(-1) != nineq)
-            or (kappa.dim() == 2 and nBatch > 1 and kappa.size(0) != nBatch)):
-        raise ValueError("qpth_amd: kappa has shape %s; expected (nBatch, %d), (%d,) or ()" % (tuple(kappa.shape), nineq, nineq))
-    return kappa
+    return _row_param(kappa, "kappa", Q, nineq, nBatch)
 
 
 def as_lower(lower, Q, nineq, nBatch=1):
     """The lower bounds of two-sided rows as every entry point takes them, as as_rho takes shapes: a tensor of Q's
     dtype and device, shape (nBatch, nineq) or (nineq,) (shared by the batch); -inf = a one-sided row.  Raises ValueError
     otherwise; the VALUES (below h, not NaN, not +inf) are checked by the loop kernel."""
-    if not torch.is_tensor(lower):
-        raise ValueError("qpth_amd: lower must be a tensor of shape (nBatch, %d) or (%d,)" % (nineq, nineq))
-    if lower.dtype != Q.dtype or lower.device != Q.device:
-        raise ValueError("qpth_amd: lower is %s on %s, the QP is %s on %s" % (lower.dtype, lower.device, Q.dtype, Q.device))
-    if lower.dim() not in (1, 2) or lower.size(-1) != nineq or (lower.dim() == 2 and nBatch > 1 and lower.size(0) != nBatch):
-        raise ValueError("qpth_amd: lower has shape %s; expected (nBatch, %d) or (%d,)" % (tuple(lower.shape), nineq, nineq))
-    return lower
+    return _row_param(lower, "lower", Q, nineq, nBatch, scalar_ok=False)
 
 
 def as_l1(l1, Q, nineq, nBatch=1):
     """The linear penalties of elastic rows as every entry point takes them, as as_rho: a tensor of Q's dtype and
     device, shape (nBatch, nineq), (nineq,) or (), or a Python number (-> a 0-dim tensor).  Raises ValueError otherwise; the
     VALUES (>= 0, +inf = a hard row) are checked by the loop kernel."""
-    if not torch.is_tensor(l1):
-        l1 = torch.tensor(float(l1), dtype=Q.dtype, device=Q.device)
-    if l1.dtype != Q.dtype or l1.device != Q.device:
-        raise ValueError("qpth_amd: l1 is %s on %s, the QP is %s on %s" % (l1.dtype, l1.device, Q.dtype, Q.device))
-    if l1.dim() > 2 or (l1.dim() >= 1 and l1.size(-1) != nineq) or (l1.dim() == 2 and nBatch > 1 and l1.size(0) != nBatch):
-        raise ValueError("qpth_amd: l1 has shape %s; expected (nBatch, %d), (%d,) or ()" % (tuple(l1.shape), nineq, nineq))
-    return l1
+    return _row_param(l1, "l1", Q, nineq, nBatch)
+
+
+def _rows(x, nineq, detach=True):
+    """a per-row parameter of any of its shapes as rows (nBatch | 1, nineq), detached"""
+    if detach:
+        x = x.detach()
+    return x.expand(nineq).unsqueeze(0) if x.dim() < 2 else x
+
+
+def _reduce_like(g, dim):
+    """a per-QP gradient (nBatch, nineq) reduced to the shape of the caller's input of `dim` dimensions: `.mean(0)` below two
+    (shared by the batch), summed over the rows as well at zero (a scalar)"""
+    if dim < 2:
+        g = g.mean(0)
+    if dim == 0:
+        g = g.sum()
+    return g
 
 
 class SoftRange:
@@ -175,18 +183,7 @@ class SoftRange:
     def fields(self, Q, nineq, nBatch=1):
         """the five fields as tensors of Q's dtype and device (a number -> a 0-dim tensor), shapes checked as as_rho does;
         the VALUES are checked by the loop kernel"""
-        out = []
-        for name in self.__slots__:
-            x = getattr(self, name)
-            if not torch.is_tensor(x):
-                x = torch.tensor(float(x), dtype=Q.dtype, device=Q.device)
-            if x.dtype != Q.dtype or x.device != Q.device:
-                raise ValueError("qpth_amd: soft_range.%s is %s on %s, the QP is %s on %s" % (name, x.dtype, x.device, Q.dtype, Q.device))
-            if x.dim() > 2 or (x.dim() >= 1 and x.size(-1) != nineq) or (x.dim() == 2 and nBatch > 1 and x.size(0) != nBatch):
-                raise ValueError("qpth_amd: soft_range.%s has shape %s; expected (nBatch, %d), (%d,) or ()"
-                                 % (name, tuple(x.shape), nineq, nineq))
-            out.append(x)
-        return out
+        return [_row_param(getattr(self, name), "soft_range." + name, Q, nineq, nBatch) for name in self.__slots__]
 
 
 class _PinnedPool:
@@ -246,6 +243,8 @@ _PINNED = _PinnedPool()
 
 
 class KKTFactors:
+    _entry_words = None      # (status and bad-entry words, event, messages) of a row role's launch, until raise_on_failure reads them
+
     @classmethod
     def build(cls, Q, G, A, nBatch=None, wide=False, w=None):
         """pre_factor_kkt(Q, G, A)   (batch.py:375-429); enqueues one kernel, no host sync.
@@ -285,7 +284,8 @@ class KKTFactors:
         self.lib = _lib.backend_for(Q)
         self.dtype, self.device = Q.dtype, Q.device
         self.Q, self.G, self.A = Q, G, (A if self.q else None)     # the original data: iterative refinement evaluates residuals with it
-        code = _lib.QPX_F32_WIDE if self.wide else (_lib.QPX_F64 if Q.dtype == torch.float64 else _lib.QPX_F32)
+        # the dtype code of every call on these factors (include/qpx.h)
+        self.code = code = _lib.QPX_F32_WIDE if self.wide else (_lib.QPX_F64 if Q.dtype == torch.float64 else _lib.QPX_F32)
         self.elems = self.lib.factor_elems(code, self.n, self.m, self.q)
         # the A/B knob of the library is per host thread and selects the blob layout: remember the value the
         # factors are built under and re-apply it around every later call on them (autograd runs backward
@@ -370,22 +370,22 @@ class KKTFactors:
         mask = _lib.ST_Q_NOT_SPD | _lib.ST_A_RANK
         if self.soft:
             mask |= _lib.ST_NONFINITE
-        bad_lower = False
-        rng, self._range = getattr(self, "_range", None), None
-        if rng is not None:
-            # two-sided rows: the words ipm_range copied in FRONT of its loop launch -- the pre-factorisation's status and, per
-            # QP, whether a lower entry is NaN, +inf or not below its h (the loop's own test, formed by torch operations): they
-            # stand in for the read-back of the pre-factorisation's words, and the host still never waits for the loop
-            host, ev = rng[:2]
+        bad_entry = None
+        staged, self._entry_words = self._entry_words, None
+        if staged is not None:
+            # the row roles (ipm_range, ipm_elastic, ipm_soft_range): the words _stage_entry_checks copied in FRONT of the loop
+            # launch -- the pre-factorisation's status and, per check and QP, whether an entry fails the loop's own test (formed
+            # by torch operations): they stand in for the read-back of the pre-factorisation's words, and the host still never
+            # waits for the loop
+            host, ev, msgs = staged
             if ev is not None:
                 ev.synchronize()
             words = host.cpu().numpy()
             self._pre_bits = int(np.bitwise_or.reduce(words[0]))      # (a later call reads these, not the pinned buffer)
             st = self._pre_bits & mask
-            # (elastic rows, ipm_elastic: a word per QP for a bad gamma and one for a bad rho instead, with their messages)
-            for row, msg in zip(words[1:], rng[2] if len(rng) > 2 else ("lower must be below h",)):
+            for row, msg in zip(words[1:], msgs):
                 if row.any():
-                    bad_lower = bad_lower or msg
+                    bad_entry = bad_entry or msg
             if self._pre_host is not None:
                 self._release_pinned(False)
         elif self._pre_soft is not None:
@@ -411,8 +411,8 @@ a non-zero diagonal.
                                "the equality constraints must have full row rank.")
         if st & _lib.ST_NONFINITE:
             raise ValueError("rho must be positive")
-        if bad_lower:
-            raise ValueError(bad_lower)
+        if bad_entry:
+            raise ValueError(bad_entry)
 
     def _no_refine_on_soft(self, refine, what):
         """refinement evaluates residuals from the caller's Q, G, A: of the HARD QP"""
@@ -439,6 +439,39 @@ a non-zero diagonal.
             X = X.reshape(1, k).expand(self.B, k)
         return X.contiguous()
 
+    def _check_ph(self, p, h):
+        self._check(p, self.n, "p")
+        self._check(h, self.m, "h")
+
+    def _check_b(self, b, b_required=True):
+        """b_required: equality rows with an empty b are an error of their own (the loop's entry points; polish and centre
+        leave an empty b to _check)"""
+        if self.q:
+            if b_required and (b is None or b.nelement() == 0):
+                raise RuntimeError("qpth_amd: A has %d rows but b is empty" % self.q)
+            self._check(b, self.q, "b")
+
+    def _new_result(self, maxIter, want_trace, more=()):
+        """an IpmResult for one loop launch: zhat, nu, lam, slacks, every field of `more` (B, nineq), iters, best_resid, the
+        trace; `status` is the factors' own words"""
+        B, dt, dev = self.B, self.dtype, self.device
+        r = IpmResult()
+        r.zhat = torch.empty(B, self.n, dtype=dt, device=dev)
+        r.nu = torch.empty(B, self.q, dtype=dt, device=dev)
+        r.lam = torch.empty(B, self.m, dtype=dt, device=dev)
+        r.slacks = torch.empty(B, self.m, dtype=dt, device=dev)
+        for name in more:
+            setattr(r, name, torch.empty(B, self.m, dtype=dt, device=dev))
+        r.iters = torch.empty(B, dtype=torch.int32, device=dev)                # written on every path of the loop kernels
+        r.best_resid = torch.empty(B, dtype=dt, device=dev)
+        r.trace = torch.full((maxIter, B, 3), float('nan'), dtype=dt, device=dev) if want_trace else None
+        r.status = self.status
+        r._warm_used = None
+        return r
+
+    def _stall(self, stall_policy):
+        return default_stall_policy(self.B) if stall_policy is None else stall_policy
+
     # -- forward (batch.py:47-207) -------------------------------------------------------
     def ipm(self, p, h, b, eps=1e-12, maxIter=20, notImprovedLim=3, stall_policy=None, want_trace=False,
             warm=None, warm_floor=1e-2):
@@ -450,17 +483,7 @@ a non-zero diagonal.
         `result.warm_used`, int32 (B,): 1 where it did.  Where the kernel family has no warm entry (qpx_warm_supported: the
         large-QP family) the call is the cold one and warm_used is zeros -- no error."""
         B, n, m, q = self.B, self.n, self.m, self.q
-        dt, dev = self.dtype, self.device
-        r = IpmResult()
-        r.zhat = torch.empty(B, n, dtype=dt, device=dev)
-        r.nu = torch.empty(B, q, dtype=dt, device=dev)
-        r.lam = torch.empty(B, m, dtype=dt, device=dev)
-        r.slacks = torch.empty(B, m, dtype=dt, device=dev)
-        r.iters = torch.empty(B, dtype=torch.int32, device=dev)                # written on every path of the loop kernels
-        r.best_resid = torch.empty(B, dtype=dt, device=dev)
-        r.trace = torch.full((maxIter, B, 3), float('nan'), dtype=dt, device=dev) if want_trace else None
-        r.status = self.status
-        r._warm_used = None
+        r = self._new_result(maxIter, want_trace)
         kw = {}
         if warm is not None:
             lam0, s0 = warm
@@ -468,41 +491,65 @@ a non-zero diagonal.
                 raise ValueError("qpth_amd: warm_floor must be positive and finite, got %r" % (warm_floor,))
             self._check(lam0, m, "warm[0] (lam0)")
             self._check(s0, m, "warm[1] (s0)")
-            code = _lib.QPX_F32_WIDE if self.wide else (_lib.QPX_F64 if dt == torch.float64 else _lib.QPX_F32)
             with self._knob():
-                served = bool(self.lib.dll.qpx_warm_supported(code, n, m, q))
+                served = bool(self.lib.dll.qpx_warm_supported(self.code, n, m, q))
             if served:
-                r._warm_used = torch.empty(B, dtype=torch.int32, device=dev)          # the kernel writes every QP's word
+                r._warm_used = torch.empty(B, dtype=torch.int32, device=self.device)          # the kernel writes every QP's word
                 kw = dict(lam0=self._vec(lam0, m, "warm[0] (lam0)"), s0=self._vec(s0, m, "warm[1] (s0)"),
                           warm_floor=warm_floor, warm_used=r._warm_used)
-        if stall_policy is None:
-            stall_policy = default_stall_policy(B)
-        self._check(p, n, "p")
-        self._check(h, m, "h")
-        if q:
-            if b is None or b.nelement() == 0:
-                raise RuntimeError("qpth_amd: A has %d rows but b is empty" % q)
-            self._check(b, q, "b")
+        self._check_ph(p, h)
+        self._check_b(b)
         with self._knob():
             self.lib.ipm(B, n, m, q, p, h, b if q else None, self.blob, self.sfac, eps, maxIter, notImprovedLim,
-                         stall_policy, r.zhat, r.nu if q else None, r.lam, r.slacks, r.iters, self.status,
+                         self._stall(stall_policy), r.zhat, r.nu if q else None, r.lam, r.slacks, r.iters, self.status,
                          r.best_resid, r.trace, wide=self.wide, **kw)
         return r
+
+    # -- what the float64 roles beside the hard loop share: range, elastic, soft range, centre ---------------
+    def _role_ok(self, symbol):
+        """does the role whose qpx_*_supported is `symbol` serve these factors (under the knob they were built with)?  float64
+        tensors, the thread-grid / tile kernels' sizes (nz+neq+nineq <= 208), HARD factors"""
+        if self.soft or self.wide or self.dtype != torch.float64 or not hasattr(self.lib.dll, symbol):
+            return False
+        with self._knob():
+            return bool(getattr(self.lib.dll, symbol)(_lib.QPX_F64, self.n, self.m, self.q))
+
+    # per role what _require_role takes: its qpx_*_supported, the rows as the refusal names them, the way out
+    _RANGE = ("qpx_range_supported", "two-sided rows (lower)", "Write the rows as [G; -G] z <= [h; -lower]")
+    _ELASTIC = ("qpx_elastic_supported", "elastic rows (l1)", "Write the augmented dense QP in (z, t)")
+    _SOFT_RANGE = ("qpx_soft_range_supported", "soft two-sided rows (soft_range)", "Write the augmented dense QP in (z, tu, tl)")
+
+    def _require_role(self, symbol, rows, way_out):
+        if not self._role_ok(symbol):
+            raise ValueError("qpth_amd: %s are served for float64 tensors up to nz + neq + nineq = 208 under the default knob, on hard "
+                             "factors; got %s, nz = %d, nineq = %d, neq = %d%s.  %s instead"
+                             % (rows, str(self.dtype).replace("torch.", ""), self.n, self.m, self.q,
+                                ", soft rows" if self.soft else "", way_out))
+
+    def _stage_entry_checks(self, r, msgs, *bad):
+        """In front of a row role's loop launch.  `r.status` becomes the status words of THIS launch: a copy of the
+        pre-factorisation's that the loop ORs its bits into -- a bad entry's QPX_ST_NONFINITE stays with the launch that met it,
+        the factors' own words never see it.  bad: per message of `msgs` a bool tensor (B | 1, nineq) or (nineq,), true where an
+        entry fails the loop's own test.  One int32 word per test and QP, stacked under the factors' status words, is
+        what raise_on_failure reads: copied to pinned memory here (no stream capture: there the words stay on the device and are
+        read from it), so that the host never waits for the loop."""
+        r.status = self.status.clone()
+        words = torch.stack([self.status] + [x.any(-1).expand(self.B).to(torch.int32) for x in bad])
+        if words.is_cuda and not torch.cuda.is_current_stream_capturing():
+            host = torch.empty(words.shape, dtype=torch.int32, pin_memory=True)
+            host.copy_(words, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+            self._entry_words = (host, ev, msgs)
+        else:
+            self._entry_words = (words, None, msgs)
 
     # -- two-sided rows lower <= G z <= h (DESIGN 4.11) ---------------------------------------
     def range_ok(self):
         """do qpx_ipm_range / qpx_backward_range serve these factors (under the knob they were built with)?  float64 tensors,
         the thread-grid / tile kernels' sizes (nz+neq+nineq <= 208), no soft rows"""
-        if self.soft or self.wide or self.dtype != torch.float64 or not hasattr(self.lib.dll, "qpx_range_supported"):
-            return False
-        with self._knob():
-            return bool(self.lib.dll.qpx_range_supported(_lib.QPX_F64, self.n, self.m, self.q))
+        return self._role_ok("qpx_range_supported")
 
-    def _range_refusal(self):
-        return ValueError("qpth_amd: two-sided rows (lower) are served for float64 tensors up to nz + neq + nineq = 208 under the "
-                          "default knob, on hard factors; got %s, nz = %d, nineq = %d, neq = %d%s.  Write the rows as "
-                          "[G; -G] z <= [h; -lower] instead" % (str(self.dtype).replace("torch.", ""), self.n, self.m, self.q,
-                                                                ", soft rows" if self.soft else ""))
 
     def gt1_of(self, lower, h):
         """|| G^T e ||_2 per QP, e = 1 on the one-sided rows (h - lower = +inf, the kernel's test): the doubled QP's
@@ -527,49 +574,18 @@ a non-zero diagonal.
         [G; -G_F] z <= [h; -lower_F], one launch, no host sync.  lower (B, nineq), (1, nineq) or (nineq,); -inf = a one-sided
         row.  The result has lam, slacks of the rows G z <= h and lam_lo, slacks_lo of lower <= G z (0 and +inf on a one-sided
         row).  A lower entry that is NaN, +inf or not below its h: QPX_ST_NONFINITE in `status` (raise_on_failure)."""
-        if not self.range_ok():
-            raise self._range_refusal()
+        self._require_role(*self._RANGE)
         B, n, m, q = self.B, self.n, self.m, self.q
-        dt, dev = self.dtype, self.device
-        self._check(p, n, "p")
-        self._check(h, m, "h")
+        self._check_ph(p, h)
         self._check(lower, m, "lower")
-        if q:
-            if b is None or b.nelement() == 0:
-                raise RuntimeError("qpth_amd: A has %d rows but b is empty" % q)
-            self._check(b, q, "b")
-        r = IpmResult()
-        r.zhat = torch.empty(B, n, dtype=dt, device=dev)
-        r.nu = torch.empty(B, q, dtype=dt, device=dev)
-        r.lam = torch.empty(B, m, dtype=dt, device=dev)
-        r.slacks = torch.empty(B, m, dtype=dt, device=dev)
-        r.lam_lo = torch.empty(B, m, dtype=dt, device=dev)
-        r.slacks_lo = torch.empty(B, m, dtype=dt, device=dev)
-        r.iters = torch.empty(B, dtype=torch.int32, device=dev)
-        r.best_resid = torch.empty(B, dtype=dt, device=dev)
-        r.trace = torch.full((maxIter, B, 3), float('nan'), dtype=dt, device=dev) if want_trace else None
-        # the status words of THIS launch: a copy of the pre-factorisation's that the loop ORs its bits into -- a bad lower's
-        # QPX_ST_NONFINITE stays with the launch that met it, the factors' own words never see it
-        r.status = self.status.clone()
-        r._warm_used = None
-        # ... and what raise_on_failure reads: copied to pinned memory in front of the loop launch (no stream capture: there
-        # the words stay on the device and are read from it)
-        bad = (~(lower.detach() < h.detach())).any(-1).expand(B).to(torch.int32)
-        words = torch.stack((self.status, bad))
-        if words.is_cuda and not torch.cuda.is_current_stream_capturing():
-            host = torch.empty(words.shape, dtype=torch.int32, pin_memory=True)
-            host.copy_(words, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            self._range = (host, ev)
-        else:
-            self._range = (words, None)
-        if stall_policy is None:
-            stall_policy = default_stall_policy(B)
-        gt1 = self.gt1_of(lower.detach(), h.detach())
+        self._check_b(b)
+        r = self._new_result(maxIter, want_trace, ("lam_lo", "slacks_lo"))
+        lo, hd = lower.detach(), h.detach()
+        self._stage_entry_checks(r, ("lower must be below h",), ~(lo < hd))
+        gt1 = self.gt1_of(lo, hd)
         with self._knob():
             self.lib.ipm_range(B, n, m, q, p, h, lower, gt1, b if q else None, self.blob, self.sfac, eps, maxIter,
-                               notImprovedLim, stall_policy, r.zhat, r.nu if q else None, r.lam, r.slacks, r.lam_lo,
+                               notImprovedLim, self._stall(stall_policy), r.zhat, r.nu if q else None, r.lam, r.slacks, r.lam_lo,
                                r.slacks_lo, r.iters, r.status, r.best_resid, r.trace)
         return r
 
@@ -579,26 +595,14 @@ a non-zero diagonal.
         d = du + dl, du = clamp(lam)/clamp(slacks), dl = clamp(lam_lo)/clamp(slacks_lo), and lam - lam_lo in dG; from its
         dz = v the two bounds' gradients dh = -v du/(du + dl), dlower = -v dl/(du + dl) (exactly 0 on a one-sided row) are
         elementwise operations here, as drho is."""
-        if not self.range_ok():
-            raise self._range_refusal()
+        self._require_role(*self._RANGE)
         B, n, m, q = self.B, self.n, self.m, self.q
-        dt, dev = self.dtype, self.device
-        wQ, wp, wG, wh, wA, wb, wl = [bool(w) for w in want]
-        sQ, sp, sG, sh, sA, sb, sl = [bool(s) for s in shared]
-        if q == 0:
-            wA = wb = False
-
-        def buf(flag, *shape):
-            return torch.empty(*shape, dtype=dt, device=dev) if flag else None
-
-        dQ = buf(wQ and not sQ, B, n, n)
-        dG = buf(wG and not sG, B, m, n)
-        dA = buf(wA and not sA, B, q, n)
-        dp = buf(wp and not sp, B, n)
-        db = buf(wb and not sb, B, q)
-        dx = buf((wp and sp) or (wQ and sQ) or (wG and sG) or (wA and sA), B, n)
-        dz = buf(wh or wl or (wG and sG), B, m)
-        dy = buf(q > 0 and ((wb and sb) or (wA and sA)), B, q)
+        wh, wl, sh, sl = bool(want[3]), bool(want[6]), bool(shared[3]), bool(shared[6])
+        # (dh is elementwise, below: the launch writes no dh and the tail has no shared-h contraction)
+        want = self._wanted(want[:6])
+        want[3] = False
+        grads, (dx, dz, dy) = self._grad_buffers(want, shared, dz_too=wh or wl)
+        dQ, dp, dG, _, dA, db = grads
         zh, lm, nv = self._vec(zhat, n, "zhat"), self._vec(lam, m, "lam"), self._vec(nu, q, "nu")
         ll, sll = self._vec(lam_lo, m, "lam_lo"), self._vec(slacks_lo, m, "slacks_lo")
         sk = self._vec(slacks, m, "slacks")
@@ -608,21 +612,7 @@ a non-zero diagonal.
         with self._knob():
             self.lib.backward_range(B, n, m, q, self.blob, self.sfac, zh, lm, sk, ll, sll, nv, gz, dQ, dp, dG, dA, db,
                                     self.status, dx, dz, dy)
-            if wQ and sQ:
-                dQ = torch.empty(n, n, dtype=dt, device=dev)
-                self.lib.batch_outer(dx, zh, zh, dx, 0.5, dQ)
-            if wG and sG:
-                dG = torch.empty(m, n, dtype=dt, device=dev)
-                self.lib.batch_outer(dz, zh, lm - ll, dx, 1.0, dG)
-            if wA and sA:
-                dA = torch.empty(q, n, dtype=dt, device=dev)
-                self.lib.batch_outer(dy, zh, nv, dx, 1.0, dA)
-            if wp and sp:
-                dp = torch.empty(n, dtype=dt, device=dev)
-                self.lib.batch_outer(dx, None, None, None, 1.0, dp)
-            if wb and sb:
-                db = torch.empty(q, dtype=dt, device=dev)
-                self.lib.batch_outer(dy, None, None, None, -1.0, db)
+            dQ, dp, dG, _, dA, db = self._shared_grads(grads, want, shared, (dx, dz, dy), zh, lm, nv, lam_lo=ll)
         dh = dlo = None
         if wh or wl:
             du = lm.clamp(min=1e-8) / sk.clamp(min=1e-8)
@@ -640,16 +630,7 @@ a non-zero diagonal.
     def elastic_ok(self):
         """does qpx_ipm_elastic serve these factors (under the knob they were built with)?  float64 tensors, the thread-grid /
         tile kernels' sizes (nz+neq+nineq <= 208), HARD factors (rho enters the loop, not the pre-factorisation)"""
-        if self.soft or self.wide or self.dtype != torch.float64 or not hasattr(self.lib.dll, "qpx_elastic_supported"):
-            return False
-        with self._knob():
-            return bool(self.lib.dll.qpx_elastic_supported(_lib.QPX_F64, self.n, self.m, self.q))
-
-    def _elastic_refusal(self):
-        return ValueError("qpth_amd: elastic rows (l1) are served for float64 tensors up to nz + neq + nineq = 208 under the "
-                          "default knob, on hard factors; got %s, nz = %d, nineq = %d, neq = %d%s.  Write the augmented dense QP "
-                          "in (z, t) instead" % (str(self.dtype).replace("torch.", ""), self.n, self.m, self.q,
-                                                 ", soft rows" if self.soft else ""))
+        return self._role_ok("qpx_elastic_supported")
 
     def gt1_elastic(self, gamma, rho):
         """sqrt(|| G^T 1 ||^2 + 4 k) per QP, k its elastic rows (gamma and rho finite, the kernel's test): the augmented QP's
@@ -667,52 +648,19 @@ a non-zero diagonal.
         (nineq,); +inf in either = a hard row.  The result has lam, slacks (= h + t - G zhat) of the rows and lam_t, slacks_t, t
         of t >= 0 (0, +inf and 0 on a hard row).  A gamma entry that is NaN or negative, a rho entry that is NaN or not
         positive: QPX_ST_NONFINITE in `status` (raise_on_failure)."""
-        if not self.elastic_ok():
-            raise self._elastic_refusal()
+        self._require_role(*self._ELASTIC)
         B, n, m, q = self.B, self.n, self.m, self.q
-        dt, dev = self.dtype, self.device
-        self._check(p, n, "p")
-        self._check(h, m, "h")
+        self._check_ph(p, h)
         self._check(gamma, m, "l1")
         self._check(rho, m, "rho")
-        if q:
-            if b is None or b.nelement() == 0:
-                raise RuntimeError("qpth_amd: A has %d rows but b is empty" % q)
-            self._check(b, q, "b")
-        r = IpmResult()
-        r.zhat = torch.empty(B, n, dtype=dt, device=dev)
-        r.nu = torch.empty(B, q, dtype=dt, device=dev)
-        r.lam = torch.empty(B, m, dtype=dt, device=dev)
-        r.slacks = torch.empty(B, m, dtype=dt, device=dev)
-        r.lam_t = torch.empty(B, m, dtype=dt, device=dev)
-        r.slacks_t = torch.empty(B, m, dtype=dt, device=dev)
-        r.t = torch.empty(B, m, dtype=dt, device=dev)
-        r.iters = torch.empty(B, dtype=torch.int32, device=dev)
-        r.best_resid = torch.empty(B, dtype=dt, device=dev)
-        r.trace = torch.full((maxIter, B, 3), float('nan'), dtype=dt, device=dev) if want_trace else None
-        # the status words of THIS launch, and what raise_on_failure reads, copied to pinned memory in front of the loop
-        # launch: as ipm_range does
-        r.status = self.status.clone()
-        r._warm_used = None
+        self._check_b(b)
+        r = self._new_result(maxIter, want_trace, ("lam_t", "slacks_t", "t"))
         gamma, rho = gamma.detach(), rho.detach()
-        bad_g = (~(gamma >= 0)).any(-1).expand(B).to(torch.int32)
-        bad_r = (~(rho > 0)).any(-1).expand(B).to(torch.int32)
-        words = torch.stack((self.status, bad_g, bad_r))
-        msgs = ("l1 must be non-negative", "rho must be positive")
-        if words.is_cuda and not torch.cuda.is_current_stream_capturing():
-            host = torch.empty(words.shape, dtype=torch.int32, pin_memory=True)
-            host.copy_(words, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            self._range = (host, ev, msgs)
-        else:
-            self._range = (words, None, msgs)
-        if stall_policy is None:
-            stall_policy = default_stall_policy(B)
+        self._stage_entry_checks(r, ("l1 must be non-negative", "rho must be positive"), ~(gamma >= 0), ~(rho > 0))
         gt1 = self.gt1_elastic(gamma, rho)
         with self._knob():
             self.lib.ipm_elastic(B, n, m, q, p, h, gamma, rho, gt1, b if q else None, self.blob, self.sfac, eps, maxIter,
-                                 notImprovedLim, stall_policy, r.zhat, r.nu if q else None, r.lam, r.slacks, r.lam_t,
+                                 notImprovedLim, self._stall(stall_policy), r.zhat, r.nu if q else None, r.lam, r.slacks, r.lam_t,
                                  r.slacks_t, r.t, r.iters, r.status, r.best_resid, r.trace)
         return r
 
@@ -730,16 +678,7 @@ a non-zero diagonal.
     def soft_range_ok(self):
         """does qpx_ipm_soft_range serve these factors (under the knob they were built with)?  float64 tensors, the thread-grid /
         tile kernels' sizes (nz+neq+nineq <= 208), HARD factors"""
-        if self.soft or self.wide or self.dtype != torch.float64 or not hasattr(self.lib.dll, "qpx_soft_range_supported"):
-            return False
-        with self._knob():
-            return bool(self.lib.dll.qpx_soft_range_supported(_lib.QPX_F64, self.n, self.m, self.q))
-
-    def _soft_range_refusal(self):
-        return ValueError("qpth_amd: soft two-sided rows (soft_range) are served for float64 tensors up to nz + neq + nineq = 208 "
-                          "under the default knob, on hard factors; got %s, nz = %d, nineq = %d, neq = %d%s.  Write the augmented "
-                          "dense QP in (z, tu, tl) instead" % (str(self.dtype).replace("torch.", ""), self.n, self.m, self.q,
-                                                               ", soft rows" if self.soft else ""))
+        return self._role_ok("qpx_soft_range_supported")
 
     def gt1_soft_range(self, h, lower, gamma_u, rho_u, gamma_l, rho_l):
         """sqrt(|| G^T e ||^2 + 4 (k_u + k_l)) per QP: e = 1 on the one-sided rows, k the soft sides (gamma and rho finite; a
@@ -758,58 +697,24 @@ a non-zero diagonal.
         vectors are (B, nineq), (1, nineq) or (nineq,).  The result has lam, slacks (upper rows), lam_lo, slacks_lo (lower rows),
         lam_t, slacks_t, t (tu >= 0) and lam_tl, slacks_tl, t_lo (tl >= 0); an absent side reads 0, +inf and 0.  A bad entry
         (NaN, lower not below h, l1 < 0, rho <= 0): QPX_ST_NONFINITE in `status` (raise_on_failure)."""
-        if not self.soft_range_ok():
-            raise self._soft_range_refusal()
+        self._require_role(*self._SOFT_RANGE)
         B, n, m, q = self.B, self.n, self.m, self.q
-        dt, dev = self.dtype, self.device
-        self._check(p, n, "p")
-        self._check(h, m, "h")
-        names = ("lower", "l1", "rho", "l1_lower", "rho_lower")
-        vecs = [x.detach() for x in (lower, l1, rho, l1_lower, rho_lower)]
-        for x, name in zip(vecs, names):
+        lower, l1, rho, l1_lower, rho_lower = [x.detach() for x in (lower, l1, rho, l1_lower, rho_lower)]
+        self._check_ph(p, h)
+        for x, name in zip((lower, l1, rho, l1_lower, rho_lower), SoftRange.__slots__):
             self._check(x, m, name)
-        lower, l1, rho, l1_lower, rho_lower = vecs
-        if q:
-            if b is None or b.nelement() == 0:
-                raise RuntimeError("qpth_amd: A has %d rows but b is empty" % q)
-            self._check(b, q, "b")
-        r = IpmResult()
-        r.zhat = torch.empty(B, n, dtype=dt, device=dev)
-        r.nu = torch.empty(B, q, dtype=dt, device=dev)
-        for name in ("lam", "slacks", "lam_lo", "slacks_lo", "lam_t", "slacks_t", "lam_tl", "slacks_tl", "t", "t_lo"):
-            setattr(r, name, torch.empty(B, m, dtype=dt, device=dev))
-        r.iters = torch.empty(B, dtype=torch.int32, device=dev)
-        r.best_resid = torch.empty(B, dtype=dt, device=dev)
-        r.trace = torch.full((maxIter, B, 3), float('nan'), dtype=dt, device=dev) if want_trace else None
-        # the status words of THIS launch, and what raise_on_failure reads, copied to pinned memory in front of the loop
-        # launch: as ipm_range does
-        r.status = self.status.clone()
-        r._warm_used = None
-
-        def word(bad):
-            return bad.any(-1).reshape(-1).expand(B).to(torch.int32)
-
+        self._check_b(b)
+        r = self._new_result(maxIter, want_trace, ("lam_lo", "slacks_lo", "lam_t", "slacks_t", "lam_tl", "slacks_tl", "t", "t_lo"))
         hd = h.detach()
-        words = torch.stack((self.status, word(~(lower < hd)), word(~(l1 >= 0)), word(~(rho > 0)), word(~(l1_lower >= 0)),
-                             word(~(rho_lower > 0))))
-        msgs = ("lower must be below h", "l1 must be non-negative", "rho must be positive", "l1_lower must be non-negative",
-                "rho_lower must be positive")
-        if words.is_cuda and not torch.cuda.is_current_stream_capturing():
-            host = torch.empty(words.shape, dtype=torch.int32, pin_memory=True)
-            host.copy_(words, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            self._range = (host, ev, msgs)
-        else:
-            self._range = (words, None, msgs)
-        if stall_policy is None:
-            stall_policy = default_stall_policy(B)
+        self._stage_entry_checks(r, ("lower must be below h", "l1 must be non-negative", "rho must be positive",
+                                     "l1_lower must be non-negative", "rho_lower must be positive"),
+                                 ~(lower < hd), ~(l1 >= 0), ~(rho > 0), ~(l1_lower >= 0), ~(rho_lower > 0))
         gt1 = self.gt1_soft_range(hd, lower, l1, rho, l1_lower, rho_lower)
         with self._knob():
             self.lib.ipm_soft_range(B, n, m, q, p, h, lower, l1, rho, l1_lower, rho_lower, gt1, b if q else None, self.blob,
-                                    self.sfac, eps, maxIter, notImprovedLim, stall_policy, r.zhat, r.nu if q else None, r.lam,
-                                    r.slacks, r.lam_lo, r.slacks_lo, r.lam_t, r.slacks_t, r.lam_tl, r.slacks_tl, r.t, r.t_lo,
-                                    r.iters, r.status, r.best_resid, r.trace)
+                                    self.sfac, eps, maxIter, notImprovedLim, self._stall(stall_policy), r.zhat,
+                                    r.nu if q else None, r.lam, r.slacks, r.lam_lo, r.slacks_lo, r.lam_t, r.slacks_t, r.lam_tl,
+                                    r.slacks_tl, r.t, r.t_lo, r.iters, r.status, r.best_resid, r.trace)
         return r
 
     def backward_soft_range(self, res, rho, rho_lower, dl_dz, want=(True,) * 11, shared=(False,) * 6):
@@ -898,9 +803,8 @@ a non-zero diagonal.
         ds = torch.empty(B, K, m, dtype=dt, device=dev)
         dz = torch.empty(B, K, m, dtype=dt, device=dev)
         dy = torch.empty(B, K, q, dtype=dt, device=dev) if q else None
-        code = _lib.QPX_F32_WIDE if self.wide else (_lib.QPX_F64 if dt == torch.float64 else _lib.QPX_F32)
         with self._knob():
-            one_launch = refine == 0 and bool(self.lib.dll.qpx_multi_supported(code, n, m, q))
+            one_launch = refine == 0 and bool(self.lib.dll.qpx_multi_supported(self.code, n, m, q))
             if one_launch:
                 self.lib.factor_solve_kkt_multi(B, n, m, q, K, self.blob, self.sfac, d, rx, rs, rz, ry, dx, ds, dz, dy,
                                                 self.status, wide=self.wide)
@@ -930,10 +834,8 @@ a non-zero diagonal.
                              "soft rows (w / rho): its steps evaluate the residuals of the hard QP")
         if self.polish_ok:
             B, n, m, q = self.B, self.n, self.m, self.q
-            self._check(p, n, "p")
-            self._check(h, m, "h")
-            if q:
-                self._check(b, q, "b")
+            self._check_ph(p, h)
+            self._check_b(b, b_required=False)
             if not self.refine_ok:
                 # the large-QP family has no refinement inside its KKT solves (qpx_refine_supported): the finishing steps
                 # themselves run, their solves un-refined -- QPFunction(refine=k) never asks for more
@@ -957,10 +859,7 @@ a non-zero diagonal.
     def centre_ok(self):
         """does qpx_centre serve these factors (under the knob they were built with)?  float64 tensors, the thread-grid /
         tile kernels' sizes (nz+neq+nineq <= 208), no soft rows"""
-        if self.soft or self.wide or self.dtype != torch.float64 or not hasattr(self.lib.dll, "qpx_centre_supported"):
-            return False
-        with self._knob():
-            return bool(self.lib.dll.qpx_centre_supported(_lib.QPX_F64, self.n, self.m, self.q))
+        return self._role_ok("qpx_centre_supported")
 
     def centre(self, p, h, b, res, kappa, tol=1e-9, max_steps=20):
         """Newton's method from the loop's result `res` onto the point of the central path
@@ -980,10 +879,8 @@ a non-zero diagonal.
                              % (str(self.dtype).replace("torch.", "") + (" in float64 arithmetic" if self.wide else ""),
                                 self.n, self.m, self.q))
         B, n, m, q = self.B, self.n, self.m, self.q
-        self._check(p, n, "p")
-        self._check(h, m, "h")
-        if q:
-            self._check(b, q, "b")
+        self._check_ph(p, h)
+        self._check_b(b, b_required=False)
         self._check(kappa, m, "kappa")
         for name in ("zhat", "lam", "slacks") + (("nu",) if q else ()):
             setattr(res, name, getattr(res, name).contiguous())
@@ -1041,27 +938,9 @@ a non-zero diagonal.
         None without equality constraints): what backward2 differentiates through."""
         self._no_refine_on_soft(refine, "backward")
         B, n, m, q = self.B, self.n, self.m, self.q
-        dt, dev = self.dtype, self.device
-        wQ, wp, wG, wh, wA, wb = [bool(w) for w in want]
-        sQ, sp, sG, sh, sA, sb = [bool(s) for s in shared]
-        if q == 0:
-            wA = wb = False
-
-        def buf(flag, *shape):
-            return torch.empty(*shape, dtype=dt, device=dev) if flag else None
-
-        dQ = buf(wQ and not sQ, B, n, n)
-        dG = buf(wG and not sG, B, m, n)
-        dA = buf(wA and not sA, B, q, n)
-        # per-QP vector gradients come out of the kernel as they are (dp = dx, dh = -dz, db = -dy: qp.py:157-166; the
-        # kernel writes the signs, no elementwise launches behind it); the KKT solution itself (dx, dz, dy) is only asked
-        # for when a batch-shared parameter needs it: one contraction / mean over the batch
-        dp = buf(wp and not sp, B, n)
-        dh = buf(wh and not sh, B, m)
-        db = buf(wb and not sb, B, q)
-        dx = buf((wp and sp) or (wQ and sQ) or (wG and sG) or (wA and sA) or want_sol, B, n)
-        dz = buf((wh and sh) or (wG and sG) or want_dz or want_sol, B, m)
-        dy = buf(q > 0 and ((wb and sb) or (wA and sA) or want_sol), B, q)
+        want = self._wanted(want)
+        grads, (dx, dz, dy) = self._grad_buffers(want, shared, dz_too=want_dz, sol_too=want_sol)
+        dQ, dp, dG, dh, dA, db = grads
         zh, lm, nv = self._vec(zhat, n, "zhat"), self._vec(lam, m, "lam"), self._vec(nu, q, "nu")
         gz, gl, gn = self._vec(dl_dz, n, "dl_dz"), self._vec(dl_dlam, m, "dl_dlam"), self._vec(dl_dnu, q, "dl_dnu")
         if gz is None and gl is None and gn is None:
@@ -1071,38 +950,80 @@ a non-zero diagonal.
             self.lib.backward(B, n, m, q, self.blob, self.sfac, zh, lm, self._vec(slacks, m, "slacks"), nv,
                               gz, dQ, dp, dG, dh, dA, db, self.status, dx, dz, dy,
                               refine=refine, Q=self.Q, G=self.G, A=self.A, wide=self.wide, **duals)
-        with self._knob():           # (their launches too need the factors' device current)
-            if wQ and sQ:
-                dQ = torch.empty(n, n, dtype=dt, device=dev)
-                self.lib.batch_outer(dx, zh, zh, dx, 0.5, dQ)
-            if wG and sG:
-                dG = torch.empty(m, n, dtype=dt, device=dev)
-                self.lib.batch_outer(dz, zh, lm, dx, 1.0, dG)
-            if wA and sA:
-                dA = torch.empty(q, n, dtype=dt, device=dev)
-                self.lib.batch_outer(dy, zh, nv, dx, 1.0, dA)
-            # shared vectors: the same contraction with a column of ones (ABI v8) -- `.mean(0)` in a fixed order of
-            # additions, the sign of qp.py:160-166 folded into the scale
-            if wp and sp:
-                dp = torch.empty(n, dtype=dt, device=dev)
-                self.lib.batch_outer(dx, None, None, None, 1.0, dp)
-            if wh and sh:
-                dh = torch.empty(m, dtype=dt, device=dev)
-                self.lib.batch_outer(dz, None, None, None, -1.0, dh)
-            if wb and sb:
-                db = torch.empty(q, dtype=dt, device=dev)
-                self.lib.batch_outer(dy, None, None, None, -1.0, db)
-        out = (dQ, dp, dG, dh, dA, db) + ((dz,) if want_dz else ())
+            grads = self._shared_grads(grads, want, shared, (dx, dz, dy), zh, lm, nv)
+        out = tuple(grads) + ((dz,) if want_dz else ())
         return out + ((dx, dz, dy),) if want_sol else out
+
+    def _wanted(self, want):
+        """the six `want` flags (Q, p, G, h, A, b) of a backward as a list of bools: none for A and b without equality constraints"""
+        want = [bool(w) for w in want]
+        if self.q == 0:
+            want[4] = want[5] = False
+        return want
+
+    def _grad_buffers(self, want, shared, dz_too=False, sol_too=False):
+        """What a backward launch writes, for six `want` (_wanted) and `shared` flags: ([dQ, dp, dG, dh, dA, db], (dx, dz, dy)),
+        None where not asked for.  Per-QP gradients come out of the kernel as they are (dp = dx, dh = -dz, db = -dy:
+        qp.py:157-166; the kernel writes the signs, no elementwise launches behind it); the KKT solution itself (dx, dz, dy) is
+        only asked for when a batch-shared parameter needs it -- one contraction / mean over the batch, _shared_grads -- or the
+        caller does (dz_too; sol_too: all three)."""
+        B, n, m, q = self.B, self.n, self.m, self.q
+        wQ, wp, wG, wh, wA, wb = want
+        sQ, sp, sG, sh, sA, sb = shared[:6]
+
+        def buf(flag, *shape):
+            return torch.empty(*shape, dtype=self.dtype, device=self.device) if flag else None
+
+        dQ = buf(wQ and not sQ, B, n, n)
+        dG = buf(wG and not sG, B, m, n)
+        dA = buf(wA and not sA, B, q, n)
+        dp = buf(wp and not sp, B, n)
+        dh = buf(wh and not sh, B, m)
+        db = buf(wb and not sb, B, q)
+        dx = buf((wp and sp) or (wQ and sQ) or (wG and sG) or (wA and sA) or sol_too, B, n)
+        dz = buf((wh and sh) or (wG and sG) or dz_too or sol_too, B, m)
+        dy = buf(q > 0 and ((wb and sb) or (wA and sA) or sol_too), B, q)
+        return [dQ, dp, dG, dh, dA, db], (dx, dz, dy)
+
+    def _shared_grads(self, grads, want, shared, sol, zh, lm, nv, lam_lo=None):
+        """The gradients of the parameters the batch shares, from the KKT solution `sol` a backward launch wrote: the
+        reference's `.mean(0)` (qp.py:159-177) as one contraction over the batch each (qpx_batch_outer), in the order Q, G, A,
+        p, h, b.  lam_lo: the range role's dG meets lam - lam_lo.  Returns `grads` with those entries filled in.  Called inside
+        the caller's _knob() block, behind its launch (these launches too need the factors' device current)."""
+        n, m, q = self.n, self.m, self.q
+        dt, dev = self.dtype, self.device
+        dx, dz, dy = sol
+        sQ, sp, sG, sh, sA, sb = shared[:6]
+        wQ, wp, wG, wh, wA, wb = want
+        if wQ and sQ:
+            grads[0] = torch.empty(n, n, dtype=dt, device=dev)
+            self.lib.batch_outer(dx, zh, zh, dx, 0.5, grads[0])
+        if wG and sG:
+            grads[2] = torch.empty(m, n, dtype=dt, device=dev)
+            self.lib.batch_outer(dz, zh, lm if lam_lo is None else lm - lam_lo, dx, 1.0, grads[2])
+        if wA and sA:
+            grads[4] = torch.empty(q, n, dtype=dt, device=dev)
+            self.lib.batch_outer(dy, zh, nv, dx, 1.0, grads[4])
+        # shared vectors: the same contraction with a column of ones (ABI v8) -- `.mean(0)` in a fixed order of
+        # additions, the sign of qp.py:160-166 folded into the scale
+        if wp and sp:
+            grads[1] = torch.empty(n, dtype=dt, device=dev)
+            self.lib.batch_outer(dx, None, None, None, 1.0, grads[1])
+        if wh and sh:
+            grads[3] = torch.empty(m, dtype=dt, device=dev)
+            self.lib.batch_outer(dz, None, None, None, -1.0, grads[3])
+        if wb and sb:
+            grads[5] = torch.empty(q, dtype=dt, device=dev)
+            self.lib.batch_outer(dy, None, None, None, -1.0, grads[5])
+        return grads
 
     # -- the backward of the backward (DESIGN 4.9) ------------------------------------------------
     def backward2_fused(self):
         """does qpx_backward2 serve these factors (under the knob they were built with)?"""
         if self.soft or not hasattr(self.lib.dll, "qpx_backward2_supported"):
             return False
-        code = _lib.QPX_F32_WIDE if self.wide else (_lib.QPX_F64 if self.dtype == torch.float64 else _lib.QPX_F32)
         with self._knob():
-            return bool(self.lib.dll.qpx_backward2_supported(code, self.n, self.m, self.q))
+            return bool(self.lib.dll.qpx_backward2_supported(self.code, self.n, self.m, self.q))
 
     def backward2(self, zhat, lam, slacks, nu, sol, W, want=(True,) * 6, fused=None):
         """The second-order pass: for cotangents W = (W_Q, W_p, W_G, W_h, W_A, W_b) on the six PER-QP gradients a call of

@@ -34,7 +34,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .kkt import KKTFactors, SoftRange, as_kappa, as_l1, as_lower, as_rho
+from .kkt import KKTFactors, SoftRange, _reduce_like, _rows, as_kappa, as_l1, as_lower, as_rho
 from .solvers.pdipm import batch as pdipm_b
 from .util import expandParam, extract_nBatch
 
@@ -51,6 +51,107 @@ def _print_trace(res):
         row = tr[i][iters > i]
         print('iter: {}, pri_resid: {:.5e}, dual_resid: {:.5e}, mu: {:.5e}'.format(
             i, row[:, 0].mean(), row[:, 1].mean(), row[:, 2].mean()))
+
+
+def _nbatch(params, extras=()):
+    """nBatch of a call: the six parameters' (extract_nBatch) or that of an extra input given per QP, (nBatch, nineq)"""
+    nBatch = extract_nBatch(*params)
+    for X in extras:
+        if X is not None and X.dim() == 2:
+            nBatch = max(nBatch, X.size(0))
+    return nBatch
+
+
+def _expand_params(params, nBatch):
+    """-> (the six parameters broadcast over the batch, for each whether the batch shares it): expandParam of each"""
+    Q, p, G, h, A, b = params
+    Q, sQ = expandParam(Q, nBatch, 3)
+    p, sp = expandParam(p, nBatch, 2)
+    G, sG = expandParam(G, nBatch, 3)
+    h, sh = expandParam(h, nBatch, 2)
+    A, sA = expandParam(A, nBatch, 3)
+    b, sb = expandParam(b, nBatch, 2)
+    return (Q, p, G, h, A, b), (sQ, sp, sG, sh, sA, sb)
+
+
+def _shared_flags(params):
+    """for each of the six parameters as the caller gave them: does the batch share it (what expandParam answers, no views made)"""
+    Q, p, G, h, A, b = params
+    return (Q.dim() == 2 and Q.nelement() > 0, p.dim() == 1 and p.nelement() > 0, G.dim() == 2 and G.nelement() > 0,
+            h.dim() == 1 and h.nelement() > 0, A.dim() == 2 and A.nelement() > 0, b.dim() == 1 and b.nelement() > 0)
+
+
+def _neq_of(A):
+    return A.size(-2) if A.nelement() > 0 else 0
+
+
+def _without_A_b(grads, neq):
+    """no equality constraints: no gradients for A and b"""
+    return grads[:4] + (None, None) + grads[6:] if neq == 0 else grads
+
+
+def _hard_factors(ctx, six, extras):
+    """What the forwards of the three row-role nodes begin with: nBatch (an extra input given per QP counts), the six
+    parameters broadcast over it, ctx.neq, and the factors of the HARD QP.  -> (nBatch, p, h, b, fac)"""
+    nBatch = _nbatch(six, extras)
+    (Q, p, G, h, A, b), _ = _expand_params(six, nBatch)
+    ctx.neq = _neq_of(six[4])
+    return nBatch, p, h, b, KKTFactors.build(Q, G, A, nBatch)
+
+
+def _loop_epilogue(fac, res, check_Q_spd, verbose, inaccurate=True):
+    """behind the launches of a forward: one small read-back -- the reference raises here too (qp.py:81-85, batch.py:379-386),
+    and so does a bad entry of a row kind's extra inputs --, the trace, and the reference's warning (batch.py:141-142,205-206;
+    `inaccurate`: the barrier-smoothed call has a check of its own instead)"""
+    fac.raise_on_failure(check_Q_spd)
+    if verbose == 1:
+        _print_trace(res)
+    if inaccurate and verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
+        print(pdipm_b.INACC_ERR)
+
+
+def _mark_duals(ctx, neq, nus, slacks):
+    """duals=True: an output the loss does not use hands backward None instead of a tensor of zeros; slacks (and nu without
+    equality constraints) are no differentiable outputs"""
+    ctx.set_materialize_grads(False)
+    if neq == 0:
+        ctx.mark_non_differentiable(slacks, nus)
+    else:
+        ctx.mark_non_differentiable(slacks)
+
+
+# The row kinds behind QPFunction's extra inputs.  kind: (label, way out, what exists in float64 arithmetic only, qpx_*_supported,
+# refusals in the order they are checked).  A refusal: (the extra input or the option of the call that the kind does not combine
+# with, the text of the message between label and way out).
+_WITH_RHO = " together with rho (soft rows) is not served"
+_WITH_KAPPA = " together with kappa (the barrier-smoothed QP) is not served"
+_WITH_LOWER = " together with lower (two-sided rows) is not served"
+_IN_HOLDER = " together with %s is not served: the SoftRange holder carries the bounds and penalties"
+_DUALS = " with duals=True is not served (the multipliers are no outputs of this node)"
+_WARM = " with warm_start is not served"
+_REFINE = " with refine=%(refine)d is not served: pass refine=0 or refine=None"
+_SOLVER = " is served by solver=QPSolvers.PDIPM_BATCHED only"
+_ROW_KINDS = {
+    "soft_range": ("qpth_amd: soft_range (soft two-sided rows)", "; write the augmented dense QP in (z, tu, tl) instead",
+                   "soft-range role", "qpx_soft_range_supported",
+                   (("rho", _IN_HOLDER % "rho"), ("kappa", _IN_HOLDER % "kappa"), ("lower", _IN_HOLDER % "lower"),
+                    ("l1", _IN_HOLDER % "l1"), ("duals", _DUALS), ("warm_start", _WARM), ("refine", _REFINE), ("solver", _SOLVER))),
+    "l1": ("qpth_amd: l1 (elastic rows)", "; write the augmented dense QP in (z, t) instead", "elastic role", "qpx_elastic_supported",
+           (("kappa", _WITH_KAPPA), ("lower", _WITH_LOWER), ("warm_start", _WARM), ("refine", _REFINE), ("solver", _SOLVER))),
+    "lower": ("qpth_amd: lower (two-sided rows)", "; write the rows as [G; -G] z <= [h; -lower] instead", "range role",
+              "qpx_range_supported",
+              (("rho", _WITH_RHO), ("kappa", _WITH_KAPPA), ("solver", _SOLVER), ("refine", _REFINE), ("duals", _DUALS),
+               ("warm_start", _WARM))),
+    "kappa": ("qpth_amd: kappa (the barrier-smoothed QP)", "", "centring kernel", "qpx_centre_supported",
+              (("rho", _WITH_RHO + ": the centring steps evaluate the residuals of the hard QP"), ("solver", _SOLVER),
+               ("refine", " with refine=%(refine)d: the centring launch already iterates on the residuals of the caller's data; "
+                          "pass refine=0 or refine=None"))),
+}
+
+
+_EXTRA_INPUTS = ("rho", "kappa", "lower", "l1")
+_OPTIONS = ("duals", "warm_start", "refine", "solver")
+assert all(name in _EXTRA_INPUTS + _OPTIONS for kind in _ROW_KINDS.values() for name, _ in kind[4])
 
 
 def f64_arithmetic_serves(nz, nineq, neq, lib=None):
@@ -183,22 +284,13 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
     nz = nineq = 500, twice the float32 family's); a batch that only fits HBM with float32 factors should pass refine=2
     (float32 kernels + finishing iterations) or refine=0 explicitly."""
     def _forward(ctx, Q_, p_, G_, h_, A_, b_, rho_=None, kappa_=None, loop_eps=None):
-        nBatch = extract_nBatch(Q_, p_, G_, h_, A_, b_)
-        if rho_ is not None and rho_.dim() == 2:
-            nBatch = max(nBatch, rho_.size(0))
-        if kappa_ is not None and kappa_.dim() == 2:
-            nBatch = max(nBatch, kappa_.size(0))
+        nBatch = _nbatch((Q_, p_, G_, h_, A_, b_), (rho_, kappa_))
         nineq, nz = G_.size(-2), G_.size(-1)
-        neq = A_.size(-2) if A_.nelement() > 0 else 0
+        neq = _neq_of(A_)
         # float32 data, float64 arithmetic (see QPFunction.__doc__)
         ctx.wide = (solver == QPSolvers.PDIPM_BATCHED and refine is None and Q_.dtype == torch.float32
                     and f64_arithmetic_serves(nz, nineq, neq, _lib.backend_for(Q_)))
-        Q, _ = expandParam(Q_, nBatch, 3)
-        p, _ = expandParam(p_, nBatch, 2)
-        G, _ = expandParam(G_, nBatch, 3)
-        h, _ = expandParam(h_, nBatch, 2)
-        A, _ = expandParam(A_, nBatch, 3)
-        b, _ = expandParam(b_, nBatch, 2)
+        (Q, p, G, h, A, b), _ = _expand_params((Q_, p_, G_, h_, A_, b_), nBatch)
 
         assert(neq > 0 or nineq > 0)
         ctx.neq, ctx.nineq, ctx.nz = neq, nineq, nz
@@ -209,7 +301,7 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                 raise ValueError("qpth_amd: rho with float32 inputs at nz = %d, nineq = %d, neq = %d, where the float32 "
                                  "kernels would run with finishing steps on the residuals of the hard QP; pass refine=0 "
                                  "(or float64 inputs)" % (nz, nineq, neq))
-            ctx.rho = rho_.detach().expand(nineq).unsqueeze(0) if rho_.dim() < 2 else rho_.detach()
+            ctx.rho = _rows(rho_, nineq)
             w = ctx.rho.reciprocal()
         else:
             w = None
@@ -224,8 +316,7 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             if kappa_ is not None:
                 # the smoothed QP: from the loop's iterate onto the central path at kappa, one more launch; ctx
                 # keeps nothing of kappa but its rank: the derivatives read the centred (lam, slacks)
-                kap = kappa_.detach().expand(nineq).unsqueeze(0) if kappa_.dim() < 2 else kappa_.detach()
-                res = fac.centre(p, h, b, res, kap, tol=kappa_tol, max_steps=kappa_steps)
+                res = fac.centre(p, h, b, res, _rows(kappa_, nineq), tol=kappa_tol, max_steps=kappa_steps)
             if ctx.refine > 0:
                 # (the solves inside a finishing step are NOT refined: the step's own residuals are exact, and refining
                 # the directions as well changes nothing in the answer -- C2 / C3 float32, two steps: the same error
@@ -233,10 +324,7 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                 res = fac.polish(p, h, b, res, steps=ctx.refine, refine=0)
             if warm_start is not None:
                 warm_start.take(res)
-            # one small read-back: the reference raises here too (qp.py:81-85, batch.py:379-386)
-            fac.raise_on_failure(check_Q_spd)
-            if verbose == 1:
-                _print_trace(res)
+            _loop_epilogue(fac, res, check_Q_spd, verbose, inaccurate=kappa_ is None)
             if kappa_ is not None:
                 # one small read-back: a QP the kernel left untouched (resid = inf after 0 steps) had a bad kappa entry
                 bad = ((res.centre_steps == 0) & torch.isinf(res.centre_resid)).any()
@@ -247,9 +335,6 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                 if off and verbose >= 0:
                     print("qpth_amd warning: centring ended above kappa_tol = %g for some QPs (worst residual %.3e after at most "
                           "%d steps); raise kappa_steps" % (kappa_tol, float(res.centre_resid.max().item()), kappa_steps))
-            elif verbose >= 0:
-                if not bool((res.best_resid <= 1.).all().item()):
-                    print(pdipm_b.INACC_ERR)                     # batch.py:141-142,205-206
             ctx.fac = fac
             zhats, ctx.nus, ctx.lams, ctx.slacks = res.zhat, res.nu, res.lam, res.slacks
         elif solver == QPSolvers.CVXPY:
@@ -272,15 +357,10 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         ctx.QGA = (Q.detach(), G.detach(), A.detach(), nBatch) if ctx.fac is None else None
         if not duals:
             return zhats
-        # the multipliers as outputs: ctx keeps detached aliases (no cycle through the outputs' grad_fn), and an output
-        # the loss does not use hands backward None instead of a tensor of zeros
+        # the multipliers as outputs: ctx keeps detached aliases (no cycle through the outputs' grad_fn)
         nus, lams, slacks = ctx.nus, ctx.lams, ctx.slacks
         ctx.nus, ctx.lams, ctx.slacks = nus.detach(), lams.detach(), slacks.detach()
-        ctx.set_materialize_grads(False)
-        if neq == 0:
-            ctx.mark_non_differentiable(slacks, nus)
-        else:
-            ctx.mark_non_differentiable(slacks)
+        _mark_duals(ctx, neq, nus, slacks)
         return zhats, nus, lams, slacks
 
     def _jvp(ctx, dQ, dp, dG, dh, dA, db, drho=None, dkappa=None):
@@ -339,15 +419,10 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             return (None, zd if need[1] else None, ld if need[2] else None, nd if need[3] else None) + tuple(H)
 
     def _backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
-        zhats, Q, p, G, h, A, b = ctx.saved_tensors[:7]
-        leaves = (Q, p, G, h, A, b)
-        nBatch = extract_nBatch(Q, p, G, h, A, b)
-        Q, Q_e = expandParam(Q, nBatch, 3)
-        p, p_e = expandParam(p, nBatch, 2)
-        G, G_e = expandParam(G, nBatch, 3)
-        h, h_e = expandParam(h, nBatch, 2)
-        A, A_e = expandParam(A, nBatch, 3)
-        b, b_e = expandParam(b, nBatch, 2)
+        saved = ctx.saved_tensors
+        zhats, leaves = saved[0], saved[1:7]
+        nBatch = extract_nBatch(*leaves)
+        shared = _shared_flags(leaves)
         neq = ctx.neq
         soft = ctx.rho_dim is not None
         smooth = ctx.kappa_dim is not None
@@ -356,6 +431,7 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
 
         fac = ctx.fac
         if fac is None:                                          # qp.py:142-143
+            (Q, _, G, _, A, _), _ = _expand_params(leaves, nBatch)
             fac = KKTFactors.build(Q, G, A, nBatch)
             fac.raise_on_failure(check_Q_spd)
 
@@ -372,41 +448,30 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             unserved = ("with soft rows (rho)" if soft else "with refine > 0 (refine=%d here)" % ctx.refine if ctx.refine > 0
                         else "on the external-solver path" if ctx.fac is None else None)
             st = dict(fac=fac, zhat=zhats.detach(), lams=ctx.lams, slacks=ctx.slacks, nus=ctx.nus, want=want,
-                      shared=(Q_e, p_e, G_e, h_e, A_e, b_e), refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0,
+                      shared=shared, refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0,
                       want_rho=want_rho, nBatch=nBatch, unserved=unserved)
             grads = QPBackwardFn.apply(st, dl_dzhat, dl_dlam, dl_dnu if neq > 0 else None, *leaves)
         else:
-            grads = fac.backward(zhats, ctx.lams, ctx.slacks, ctx.nus, dl_dzhat, want=want,
-                                 shared=(Q_e, p_e, G_e, h_e, A_e, b_e),
+            grads = fac.backward(zhats, ctx.lams, ctx.slacks, ctx.nus, dl_dzhat, want=want, shared=shared,
                                  refine=1 if (ctx.refine > 0 and fac.refine_ok) else 0,
                                  dl_dlam=dl_dlam, dl_dnu=dl_dnu if neq > 0 else None, want_dz=want_rho)
         if want_rho:
             grads, dz = grads[:6], grads[6]
-        if neq == 0:
-            grads = grads[:4] + (None, None)
+        grads = _without_A_b(grads, neq)
         if smooth:
             dkappa = None
             if want_rho:
                 # d loss / d kappa = dz / lam, reduced like drho; it carries no graph (second derivatives with respect
                 # to kappa are not offered)
-                dkappa = dz.detach() / ctx.lams
-                if ctx.kappa_dim < 2:
-                    dkappa = dkappa.mean(0)
-                if ctx.kappa_dim == 0:
-                    dkappa = dkappa.sum()
+                dkappa = _reduce_like(dz.detach() / ctx.lams, ctx.kappa_dim)
             return grads + (dkappa, None)
         if not soft:
             return grads
         drho = None
         if want_rho:
             # dw = -dz lam, w = 1 / rho: drho = dz lam / rho^2 (0 on a hard row); shared: `.mean(0)`, a scalar summed over the rows
-            rho = ctx.saved_tensors[7]
-            rho = rho.expand(ctx.nineq).unsqueeze(0) if ctx.rho_dim < 2 else rho
-            drho = dz * ctx.lams / (rho * rho)
-            if ctx.rho_dim < 2:
-                drho = drho.mean(0)
-            if ctx.rho_dim == 0:
-                drho = drho.sum()
+            rho = _rows(saved[7], ctx.nineq, detach=False)
+            drho = _reduce_like(dz * ctx.lams / (rho * rho), ctx.rho_dim)
         return grads + (drho,)
 
     class QPFunctionFn(Function):
@@ -455,24 +520,9 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         """the node of two-sided rows: lower, the seventh differentiable input, behind the six parameters"""
         @staticmethod
         def forward(ctx, Q_, p_, G_, h_, A_, b_, lower_):
-            nBatch = extract_nBatch(Q_, p_, G_, h_, A_, b_)
-            if lower_.dim() == 2:
-                nBatch = max(nBatch, lower_.size(0))
-            Q, _ = expandParam(Q_, nBatch, 3)
-            p, _ = expandParam(p_, nBatch, 2)
-            G, _ = expandParam(G_, nBatch, 3)
-            h, _ = expandParam(h_, nBatch, 2)
-            A, _ = expandParam(A_, nBatch, 3)
-            b, _ = expandParam(b_, nBatch, 2)
-            ctx.neq = A_.size(-2) if A_.nelement() > 0 else 0
-            fac = KKTFactors.build(Q, G, A, nBatch)
+            _, p, h, b, fac = _hard_factors(ctx, (Q_, p_, G_, h_, A_, b_), (lower_,))
             res = fac.ipm_range(p, h, lower_.detach(), b, eps, maxIter, notImprovedLim, want_trace=(verbose == 1))
-            # one small read-back: the reference raises here too (qp.py:81-85), and so does a lower entry not below its h
-            fac.raise_on_failure(check_Q_spd)
-            if verbose == 1:
-                _print_trace(res)
-            if verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
-                print(pdipm_b.INACC_ERR)
+            _loop_epilogue(fac, res, check_Q_spd, verbose)
             ctx.fac = fac
             ctx.nus, ctx.lams, ctx.slacks, ctx.lams_lo, ctx.slacks_lo = res.nu, res.lam, res.slacks, res.lam_lo, res.slacks_lo
             ctx.save_for_backward(res.zhat, Q_, p_, G_, h_, A_, b_, lower_)
@@ -486,14 +536,10 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         @staticmethod
         @once_differentiable
         def backward(ctx, dl_dzhat):
-            zhats, Q, p, G, h, A, b, lower = ctx.saved_tensors
-            nBatch = max(extract_nBatch(Q, p, G, h, A, b), lower.size(0) if lower.dim() == 2 else 1)
-            shared = (Q.dim() == 2, p.dim() == 1, G.dim() == 2, h.dim() == 1, A.dim() == 2, b.dim() == 1, lower.dim() == 1)
+            zhats, *six, lower = ctx.saved_tensors
             grads = ctx.fac.backward_range(zhats, ctx.lams, ctx.slacks, ctx.lams_lo, ctx.slacks_lo, ctx.nus, dl_dzhat,
-                                           want=tuple(ctx.needs_input_grad[:7]), shared=shared)
-            if ctx.neq == 0:
-                grads = grads[:4] + (None, None) + grads[6:]
-            return grads
+                                           want=tuple(ctx.needs_input_grad[:7]), shared=_shared_flags(six) + (lower.dim() == 1,))
+            return _without_A_b(grads, ctx.neq)
 
     class QPElasticFunctionFn(Function):
         """the node of elastic rows: rho and l1, the seventh and eighth differentiable inputs, behind the six parameters (DESIGN
@@ -501,28 +547,11 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         launches of the hard QP, given lam and the effective slack (KKTFactors.elastic_eff)."""
         @staticmethod
         def forward(ctx, Q_, p_, G_, h_, A_, b_, rho_, l1_):
-            nBatch = extract_nBatch(Q_, p_, G_, h_, A_, b_)
-            for X in (rho_, l1_):
-                if X.dim() == 2:
-                    nBatch = max(nBatch, X.size(0))
             nineq = G_.size(-2)
-            Q, _ = expandParam(Q_, nBatch, 3)
-            p, _ = expandParam(p_, nBatch, 2)
-            G, _ = expandParam(G_, nBatch, 3)
-            h, _ = expandParam(h_, nBatch, 2)
-            A, _ = expandParam(A_, nBatch, 3)
-            b, _ = expandParam(b_, nBatch, 2)
-            ctx.neq = neq = A_.size(-2) if A_.nelement() > 0 else 0
-            gam = l1_.detach().expand(nineq).unsqueeze(0) if l1_.dim() < 2 else l1_.detach()
-            rho = rho_.detach().expand(nineq).unsqueeze(0) if rho_.dim() < 2 else rho_.detach()
-            fac = KKTFactors.build(Q, G, A, nBatch)
+            _, p, h, b, fac = _hard_factors(ctx, (Q_, p_, G_, h_, A_, b_), (rho_, l1_))
+            gam, rho = _rows(l1_, nineq), _rows(rho_, nineq)
             res = fac.ipm_elastic(p, h, gam, rho, b, eps, maxIter, notImprovedLim, want_trace=(verbose == 1))
-            # one small read-back: the reference raises here too (qp.py:81-85), and so does a bad l1 or rho entry
-            fac.raise_on_failure(check_Q_spd)
-            if verbose == 1:
-                _print_trace(res)
-            if verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
-                print(pdipm_b.INACC_ERR)
+            _loop_epilogue(fac, res, check_Q_spd, verbose)
             ctx.fac = fac
             # a row is hard where either is +inf (the kernel's rule): rho = +inf there for the derivatives' formulas
             ctx.rho = torch.where(torch.isfinite(gam), rho, torch.full_like(rho, float("inf")))
@@ -533,11 +562,7 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             ctx.save_for_backward(Q_, p_, G_, h_, A_, b_, rho_, l1_)
             if not duals:
                 return res.zhat
-            ctx.set_materialize_grads(False)
-            if neq == 0:
-                ctx.mark_non_differentiable(res.slacks, res.nu)
-            else:
-                ctx.mark_non_differentiable(res.slacks)
+            _mark_duals(ctx, ctx.neq, res.nu, res.slacks)
             return res.zhat, res.nu, res.lam, res.slacks
 
         @staticmethod
@@ -555,11 +580,10 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         @staticmethod
         @once_differentiable
         def backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
-            Q, p, G, h, A, b = ctx.saved_tensors[:6]
             neq = ctx.neq
             if dl_dzhat is None and dl_dlam is None and (dl_dnu is None or neq == 0):
                 return (None,) * 8
-            shared = (Q.dim() == 2, p.dim() == 1, G.dim() == 2, h.dim() == 1, A.dim() == 2, b.dim() == 1)
+            shared = _shared_flags(ctx.saved_tensors[:6])
             want_pen = ctx.needs_input_grad[6] or ctx.needs_input_grad[7]
             grads = ctx.fac.backward(ctx.zhat, ctx.lams, ctx.seff, ctx.nus, dl_dzhat, want=tuple(ctx.needs_input_grad[:6]),
                                      shared=shared, dl_dlam=dl_dlam, dl_dnu=dl_dnu if neq > 0 else None, want_dz=want_pen)
@@ -569,15 +593,10 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                 # d loss / d l1 = dz / (dt + rho), d loss / d rho = t d loss / d l1; shared: `.mean(0)`, a scalar summed over the rows
                 dgam = dz / (ctx.dt + ctx.rho)
                 if ctx.needs_input_grad[7]:
-                    dl1 = dgam.mean(0) if ctx.l1_dim < 2 else dgam
-                    dl1 = dl1.sum() if ctx.l1_dim == 0 else dl1
+                    dl1 = _reduce_like(dgam, ctx.l1_dim)
                 if ctx.needs_input_grad[6]:
-                    drho = dgam * ctx.t
-                    drho = drho.mean(0) if ctx.rho_dim < 2 else drho
-                    drho = drho.sum() if ctx.rho_dim == 0 else drho
-            if neq == 0:
-                grads = grads[:4] + (None, None)
-            return grads + (drho, dl1)
+                    drho = _reduce_like(dgam * ctx.t, ctx.rho_dim)
+            return _without_A_b(grads, neq) + (drho, dl1)
 
     class QPSoftRangeFunctionFn(Function):
         """the node of soft two-sided rows: lower, l1, rho, l1_lower, rho_lower behind the six parameters.  Forward:
@@ -585,30 +604,14 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         effective slack of each side (KKTFactors.backward_soft_range)."""
         @staticmethod
         def forward(ctx, Q_, p_, G_, h_, A_, b_, *fields_):
-            nBatch = extract_nBatch(Q_, p_, G_, h_, A_, b_)
-            for X in fields_:
-                if X.dim() == 2:
-                    nBatch = max(nBatch, X.size(0))
             nineq = G_.size(-2)
-            Q, _ = expandParam(Q_, nBatch, 3)
-            p, _ = expandParam(p_, nBatch, 2)
-            G, _ = expandParam(G_, nBatch, 3)
-            h, _ = expandParam(h_, nBatch, 2)
-            A, _ = expandParam(A_, nBatch, 3)
-            b, _ = expandParam(b_, nBatch, 2)
-            ctx.neq = A_.size(-2) if A_.nelement() > 0 else 0
-            lo, gu, ru, gl, rl = [X.detach().expand(nineq).unsqueeze(0) if X.dim() < 2 else X.detach() for X in fields_]
-            fac = KKTFactors.build(Q, G, A, nBatch)
+            nBatch, p, h, b, fac = _hard_factors(ctx, (Q_, p_, G_, h_, A_, b_), fields_)
+            lo, gu, ru, gl, rl = [_rows(X, nineq) for X in fields_]
             res = fac.ipm_soft_range(p, h, lo, gu, ru, gl, rl, b, eps, maxIter, notImprovedLim, want_trace=(verbose == 1))
-            # one small read-back: the reference raises here too (qp.py:81-85), and so does a bad entry of the five fields
-            fac.raise_on_failure(check_Q_spd)
-            if verbose == 1:
-                _print_trace(res)
-            if verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
-                print(pdipm_b.INACC_ERR)
+            _loop_epilogue(fac, res, check_Q_spd, verbose)
             ctx.fac, ctx.res = fac, res
             # a side is hard where either of its penalties is +inf (the kernel's rule): rho = +inf there for the derivatives
-            inf = torch.full((nBatch, nineq), float("inf"), dtype=Q.dtype, device=Q.device)
+            inf = torch.full((nBatch, nineq), float("inf"), dtype=Q_.dtype, device=Q_.device)
             ctx.rho_u = torch.where(torch.isfinite(gu), ru, inf)
             ctx.rho_l = torch.where(torch.isfinite(gl), rl, inf)
             ctx.dims = [X.dim() for X in fields_]
@@ -623,134 +626,55 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         @staticmethod
         @once_differentiable
         def backward(ctx, dl_dzhat):
-            Q, p, G, h, A, b = ctx.saved_tensors
-            shared = (Q.dim() == 2, p.dim() == 1, G.dim() == 2, h.dim() == 1, A.dim() == 2, b.dim() == 1)
             grads = ctx.fac.backward_soft_range(ctx.res, ctx.rho_u, ctx.rho_l, dl_dzhat, want=tuple(ctx.needs_input_grad[:11]),
-                                                shared=shared)
-            six, five = grads[:6], []
+                                                shared=_shared_flags(ctx.saved_tensors))
             # an un-batched field: `.mean(0)`, a scalar summed over the rows as well (as l1 and rho of the elastic rows)
-            for g, dim in zip(grads[6:], ctx.dims):
-                if g is not None and dim < 2:
-                    g = g.mean(0)
-                    g = g.sum() if dim == 0 else g
-                five.append(g)
-            if ctx.neq == 0:
-                six = six[:4] + (None, None)
-            return six + tuple(five)
+            five = tuple(None if g is None else _reduce_like(g, dim) for g, dim in zip(grads[6:], ctx.dims))
+            return _without_A_b(grads[:6], ctx.neq) + five
 
-    def _apply_soft_range(Q, p, G, h, A, b, rho, kappa, lower, l1, soft_range):
-        what = "qpth_amd: soft_range (soft two-sided rows)"
-        out = "; write the augmented dense QP in (z, tu, tl) instead"
-        if not isinstance(soft_range, SoftRange):
-            raise ValueError(what + " must be a qpth_amd.SoftRange(lower, l1, rho, l1_lower=None, rho_lower=None), got %s"
-                             % type(soft_range).__name__)
-        for name, val in (("rho", rho), ("kappa", kappa), ("lower", lower), ("l1", l1)):
-            if val is not None:
-                raise ValueError(what + " together with %s is not served: the SoftRange holder carries the bounds and penalties" % name
-                                 + out)
-        if duals:
-            raise ValueError(what + " with duals=True is not served (the multipliers are no outputs of this node)" + out)
-        if warm_start is not None:
-            raise ValueError(what + " with warm_start is not served" + out)
-        if refine is not None and int(refine) > 0:
-            raise ValueError(what + " with refine=%d is not served: pass refine=0 or refine=None" % int(refine) + out)
-        if solver != QPSolvers.PDIPM_BATCHED:
-            raise ValueError(what + " is served by solver=QPSolvers.PDIPM_BATCHED only" + out)
-        if Q.dtype != torch.float64:
-            raise ValueError(what + " is served for float64 inputs only (the soft-range role exists in float64 arithmetic), got %s"
-                             % Q.dtype + out)
-        nineq, nz = G.size(-2), G.size(-1)
-        neq = A.size(-2) if A.nelement() > 0 else 0
-        if not _lib.backend_for(Q).dll.qpx_soft_range_supported(_lib.QPX_F64, nz, nineq, neq):
-            raise ValueError(what + " is served up to nz + neq + nineq = 208 (the thread-grid / tile kernels, "
-                             "qpx_soft_range_supported); got nz = %d, nineq = %d, neq = %d" % (nz, nineq, neq) + out)
-        fields = soft_range.fields(Q, nineq, extract_nBatch(Q, p, G, h, A, b))
-        return QPSoftRangeFunctionFn.apply(Q, p, G, h, A, b, *fields)
+    # the options of this QPFunction(...) that a row kind may refuse (_ROW_KINDS): is each one set?
+    option_set = {"duals": bool(duals), "warm_start": warm_start is not None, "refine": refine is not None and int(refine) > 0,
+                  "solver": solver != QPSolvers.PDIPM_BATCHED}
 
-    def _apply_elastic(Q, p, G, h, A, b, rho, kappa, lower, l1):
-        what = "qpth_amd: l1 (elastic rows)"
-        out = "; write the augmented dense QP in (z, t) instead"
-        if rho is None:
-            raise ValueError(what + " needs rho: rho is the penalty's curvature, gamma't + 1/2 t'diag(rho)t, and the pure l1 penalty "
-                             "(rho = 0, a singular augmented Q) is not served")
-        if kappa is not None:
-            raise ValueError(what + " together with kappa (the barrier-smoothed QP) is not served" + out)
-        if lower is not None:
-            raise ValueError(what + " together with lower (two-sided rows) is not served" + out)
-        if warm_start is not None:
-            raise ValueError(what + " with warm_start is not served" + out)
-        if refine is not None and int(refine) > 0:
-            raise ValueError(what + " with refine=%d is not served: pass refine=0 or refine=None" % int(refine) + out)
-        if solver != QPSolvers.PDIPM_BATCHED:
-            raise ValueError(what + " is served by solver=QPSolvers.PDIPM_BATCHED only" + out)
+    def _gate(kind, Q, G, A, **given):
+        """The refusals of one row kind (_ROW_KINDS), the first that applies: the other extra inputs (`given`) and the options of
+        the call it does not combine with, in the kind's own order; then float64 inputs; then a size its role serves."""
+        what, out, exists, symbol, refusals = _ROW_KINDS[kind]
+        for name, text in refusals:
+            if (given.get(name) is not None) if name in _EXTRA_INPUTS else option_set[name]:
+                raise ValueError(what + text % {"refine": refine} + out)
         if Q.dtype != torch.float64:
-            raise ValueError(what + " is served for float64 inputs only (the elastic role exists in float64 arithmetic), got %s"
-                             % Q.dtype + out)
-        nineq, nz = G.size(-2), G.size(-1)
-        neq = A.size(-2) if A.nelement() > 0 else 0
-        if not _lib.backend_for(Q).dll.qpx_elastic_supported(_lib.QPX_F64, nz, nineq, neq):
-            raise ValueError(what + " is served up to nz + neq + nineq = 208 (the thread-grid / tile kernels, qpx_elastic_supported); "
-                             "got nz = %d, nineq = %d, neq = %d" % (nz, nineq, neq) + out)
-        nB = extract_nBatch(Q, p, G, h, A, b)
-        return QPElasticFunctionFn.apply(Q, p, G, h, A, b, as_rho(rho, Q, nineq, nB), as_l1(l1, Q, nineq, nB))
-
-    def _apply_range(Q, p, G, h, A, b, rho, kappa, lower):
-        what = "qpth_amd: lower (two-sided rows)"
-        out = "; write the rows as [G; -G] z <= [h; -lower] instead"
-        if rho is not None:
-            raise ValueError(what + " together with rho (soft rows) is not served" + out)
-        if kappa is not None:
-            raise ValueError(what + " together with kappa (the barrier-smoothed QP) is not served" + out)
-        if solver != QPSolvers.PDIPM_BATCHED:
-            raise ValueError(what + " is served by solver=QPSolvers.PDIPM_BATCHED only" + out)
-        if refine is not None and int(refine) > 0:
-            raise ValueError(what + " with refine=%d is not served: pass refine=0 or refine=None" % int(refine) + out)
-        if duals:
-            raise ValueError(what + " with duals=True is not served (the multipliers are no outputs of this node)" + out)
-        if warm_start is not None:
-            raise ValueError(what + " with warm_start is not served" + out)
-        if Q.dtype != torch.float64:
-            raise ValueError(what + " is served for float64 inputs only (the range role exists in float64 arithmetic), got %s"
-                             % Q.dtype + out)
-        nineq, nz = G.size(-2), G.size(-1)
-        neq = A.size(-2) if A.nelement() > 0 else 0
-        if not _lib.backend_for(Q).dll.qpx_range_supported(_lib.QPX_F64, nz, nineq, neq):
-            raise ValueError(what + " is served up to nz + neq + nineq = 208 (the thread-grid / tile kernels, qpx_range_supported); "
-                             "got nz = %d, nineq = %d, neq = %d" % (nz, nineq, neq) + out)
-        lower = as_lower(lower, Q, nineq, extract_nBatch(Q, p, G, h, A, b))
-        return QPRangeFunctionFn.apply(Q, p, G, h, A, b, lower)
-
-    def _apply_smooth(Q, p, G, h, A, b, rho, kappa):
-        what = "qpth_amd: kappa (the barrier-smoothed QP)"
-        if rho is not None:
-            raise ValueError(what + " together with rho (soft rows) is not served: the centring steps evaluate the residuals of "
-                             "the hard QP")
-        if solver != QPSolvers.PDIPM_BATCHED:
-            raise ValueError(what + " is served by solver=QPSolvers.PDIPM_BATCHED only")
-        if refine is not None and int(refine) > 0:
-            raise ValueError(what + " with refine=%d: the centring launch already iterates on the residuals of the caller's data; "
-                             "pass refine=0 or refine=None" % int(refine))
-        if Q.dtype != torch.float64:
-            raise ValueError(what + " is served for float64 inputs only (the centring kernel exists in float64 arithmetic), "
-                             "got %s" % Q.dtype)
-        nineq, nz = G.size(-2), G.size(-1)
-        neq = A.size(-2) if A.nelement() > 0 else 0
-        if not _lib.backend_for(Q).dll.qpx_centre_supported(_lib.QPX_F64, nz, nineq, neq):
-            raise ValueError(what + " is served up to nz + neq + nineq = 208 (the thread-grid / tile kernels, "
-                             "qpx_centre_supported); got nz = %d, nineq = %d, neq = %d" % (nz, nineq, neq))
-        loop_eps = None if torch.is_tensor(kappa) else max(float(eps), nineq * float(kappa))
-        kappa = as_kappa(kappa, Q, nineq, extract_nBatch(Q, p, G, h, A, b))
-        return QPSmoothFunctionFn.apply(Q, p, G, h, A, b, kappa, loop_eps)
+            raise ValueError(what + " is served for float64 inputs only (the %s exists in float64 arithmetic), got %s"
+                             % (exists, Q.dtype) + out)
+        nineq, nz, neq = G.size(-2), G.size(-1), _neq_of(A)
+        if not getattr(_lib.backend_for(Q).dll, symbol)(_lib.QPX_F64, nz, nineq, neq):
+            raise ValueError(what + " is served up to nz + neq + nineq = 208 (the thread-grid / tile kernels, %s); "
+                             "got nz = %d, nineq = %d, neq = %d" % (symbol, nz, nineq, neq) + out)
 
     def apply(Q, p, G, h, A, b, rho=None, kappa=None, lower=None, l1=None, soft_range=None):
+        nineq = G.size(-2)
         if soft_range is not None:
-            return _apply_soft_range(Q, p, G, h, A, b, rho, kappa, lower, l1, soft_range)
+            if not isinstance(soft_range, SoftRange):
+                raise ValueError(_ROW_KINDS["soft_range"][0] + " must be a qpth_amd.SoftRange(lower, l1, rho, l1_lower=None, "
+                                 "rho_lower=None), got %s" % type(soft_range).__name__)
+            _gate("soft_range", Q, G, A, rho=rho, kappa=kappa, lower=lower, l1=l1)
+            fields = soft_range.fields(Q, nineq, extract_nBatch(Q, p, G, h, A, b))
+            return QPSoftRangeFunctionFn.apply(Q, p, G, h, A, b, *fields)
         if l1 is not None:
-            return _apply_elastic(Q, p, G, h, A, b, rho, kappa, lower, l1)
+            if rho is None:
+                raise ValueError(_ROW_KINDS["l1"][0] + " needs rho: rho is the penalty's curvature, gamma't + 1/2 t'diag(rho)t, and "
+                                 "the pure l1 penalty (rho = 0, a singular augmented Q) is not served")
+            _gate("l1", Q, G, A, kappa=kappa, lower=lower)
+            nB = extract_nBatch(Q, p, G, h, A, b)
+            return QPElasticFunctionFn.apply(Q, p, G, h, A, b, as_rho(rho, Q, nineq, nB), as_l1(l1, Q, nineq, nB))
         if lower is not None:
-            return _apply_range(Q, p, G, h, A, b, rho, kappa, lower)
+            _gate("lower", Q, G, A, rho=rho, kappa=kappa)
+            return QPRangeFunctionFn.apply(Q, p, G, h, A, b, as_lower(lower, Q, nineq, extract_nBatch(Q, p, G, h, A, b)))
         if kappa is not None:
-            return _apply_smooth(Q, p, G, h, A, b, rho, kappa)
+            _gate("kappa", Q, G, A, rho=rho)
+            loop_eps = None if torch.is_tensor(kappa) else max(float(eps), nineq * float(kappa))
+            kappa = as_kappa(kappa, Q, nineq, extract_nBatch(Q, p, G, h, A, b))
+            return QPSmoothFunctionFn.apply(Q, p, G, h, A, b, kappa, loop_eps)
         if rho is None:
             return QPFunctionFn.apply(Q, p, G, h, A, b)
         if solver != QPSolvers.PDIPM_BATCHED:
@@ -759,6 +683,6 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         if refine is not None and int(refine) > 0:
             raise ValueError("qpth_amd: rho with refine=%d: refinement and the finishing steps evaluate residuals of the hard "
                              "QP; pass refine=0 (or refine=None with float64 inputs)" % int(refine))
-        rho = as_rho(rho, Q, G.size(-2), extract_nBatch(Q, p, G, h, A, b))
+        rho = as_rho(rho, Q, nineq, extract_nBatch(Q, p, G, h, A, b))
         return QPSoftFunctionFn.apply(Q, p, G, h, A, b, rho)
     return apply

@@ -15,10 +15,9 @@ An analysis interface, not an autograd node: every output is detached, and `QPFu
 import torch
 
 from . import _lib
-from .kkt import KKTFactors, as_kappa, as_rho
-from .qp import _print_trace, f64_arithmetic_serves
-from .solvers.pdipm import batch as pdipm_b
-from .util import expandParam, extract_nBatch
+from .kkt import KKTFactors, _rows, as_kappa, as_rho
+from .qp import _expand_params, _loop_epilogue, _neq_of, f64_arithmetic_serves
+from .util import extract_nBatch
 
 _VECTORS = ("p", "h", "b")
 _MATRICES = ("Q", "G", "A")
@@ -149,7 +148,7 @@ def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd
     with torch.no_grad():
         nBatch = extract_nBatch(Q, p, G, h, A, b)
         nineq, nz = G.size(-2), G.size(-1)
-        neq = A.size(-2) if A.nelement() > 0 else 0
+        neq = _neq_of(A)
         assert(neq > 0 or nineq > 0)
         wide = Q.dtype == torch.float32 and f64_arithmetic_serves(nz, nineq, neq, _lib.backend_for(Q))
         rho_dim = None
@@ -159,7 +158,7 @@ def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd
                 raise ValueError("qpth_amd: rho with float32 inputs at a size the float32 kernels serve with finishing steps on the "
                                  "residuals of the hard QP; use float64 inputs, or QPFunction(refine=0)")
             rho_dim = rho.dim()
-            rho = rho.detach().expand(nineq).unsqueeze(0) if rho_dim < 2 else rho.detach()
+            rho = _rows(rho, nineq)
             nBatch = max(nBatch, rho.size(0))
         if kappa is not None:
             if rho is not None:
@@ -167,11 +166,10 @@ def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd
             if Q.dtype != torch.float64:
                 raise ValueError("qpth_amd: kappa (the barrier-smoothed QP) is served for float64 inputs only, got %s" % Q.dtype)
             loop_eps = None if torch.is_tensor(kappa) else max(float(eps), nineq * float(kappa))
-            kappa = as_kappa(kappa, Q, nineq, nBatch).detach()
-            kappa = kappa.expand(nineq).unsqueeze(0) if kappa.dim() < 2 else kappa
+            kappa = _rows(as_kappa(kappa, Q, nineq, nBatch), nineq)
             nBatch = max(nBatch, kappa.size(0))
             eps = eps if loop_eps is None else loop_eps
-        params, shared = zip(*[expandParam(X.detach(), nBatch, nd) for X, nd in zip((Q, p, G, h, A, b), (3, 2, 3, 2, 3, 2))])
+        params, shared = _expand_params([X.detach() for X in (Q, p, G, h, A, b)], nBatch)
         Qe, pe, Ge, he, Ae, be = params
         fac = KKTFactors.build(Qe, Ge, Ae, nBatch, wide=wide, w=None if rho is None else rho.reciprocal())
         warm = warm_start.pair(nBatch, nineq, Q.dtype, Q.device) if warm_start is not None else None
@@ -184,12 +182,8 @@ def solve(Q, p, G, h, A, b, eps=1e-12, maxIter=20, notImprovedLim=3, check_Q_spd
             res = fac.centre(pe, he, be, res, kappa, tol=kappa_tol, max_steps=kappa_steps)      # (refuses unserved sizes)
         if warm_start is not None:
             warm_start.take(res)
-        fac.raise_on_failure(check_Q_spd)
-        if verbose == 1:
-            _print_trace(res)
+        _loop_epilogue(fac, res, check_Q_spd, verbose, inaccurate=kappa is None)
         if kappa is not None:
             if bool(((res.centre_steps == 0) & torch.isinf(res.centre_resid)).any().item()):
                 raise ValueError("kappa must be positive")
-        elif verbose >= 0 and not bool((res.best_resid <= 1.).all().item()):
-            print(pdipm_b.INACC_ERR)
         return QPSolution(fac, res, params, shared, refine, rho, rho_dim)

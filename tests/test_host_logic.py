@@ -62,6 +62,52 @@ def test_default_stall_policy_is_the_reference_counter_for_one_qp():
     assert default_stall_policy(1) == _lib.STALL_REFERENCE and default_stall_policy(2) == _lib.STALL_FLOOR
 
 
+def test_per_row_parameters_are_validated_alike_but_lower_takes_no_scalar():
+    """as_rho, as_kappa, as_l1, as_lower and SoftRange.fields: one dtype, device and shape check (no library: nothing is
+    launched); the one difference is that `lower` is neither a Python number nor a 0-dim tensor."""
+    from qpth_amd.kkt import SoftRange, as_kappa, as_l1, as_lower, as_rho
+    nineq, nBatch = 3, 2
+    Q = torch.eye(4, dtype=torch.float64)
+    ok = {"lower": torch.zeros(nBatch, nineq, dtype=torch.float64), "l1": 1.0, "rho": 1.0}
+
+    def field(name):
+        def check(x):
+            kw = dict(ok, **{name: x})
+            holder = SoftRange(kw["lower"], kw["l1"], kw["rho"], kw.get("l1_lower"), kw.get("rho_lower"))
+            return holder.fields(Q, nineq, nBatch)[SoftRange.__slots__.index(name)]
+        return check
+
+    checks = [("rho", lambda x: as_rho(x, Q, nineq, nBatch), True), ("kappa", lambda x: as_kappa(x, Q, nineq, nBatch), True),
+              ("l1", lambda x: as_l1(x, Q, nineq, nBatch), True), ("lower", lambda x: as_lower(x, Q, nineq, nBatch), False),
+              ("soft_range.lower", field("lower"), True)]
+    checks += [("soft_range." + name, field(name), True) for name in ("l1", "rho", "l1_lower", "rho_lower")]
+    assert len(checks) == 9
+    for name, check, scalar_ok in checks:
+        with pytest.raises(ValueError, match=r"qpth_amd: %s is torch\.float32" % name.replace(".", r"\.")):
+            check(torch.ones(nBatch, nineq, dtype=torch.float32))
+        for shape in ((2, 4), (3, 3), (2, 2, 3)):
+            with pytest.raises(ValueError, match=r"qpth_amd: %s has shape" % name.replace(".", r"\.")):
+                check(torch.ones(shape, dtype=torch.float64))
+        for shape in ((2, 3), (3,)):
+            x = torch.ones(shape, dtype=torch.float64)
+            out = check(x)
+            assert out is x and out.dtype == Q.dtype
+        for x in (torch.tensor(2.0, dtype=torch.float64), 2.0):
+            if scalar_ok:
+                out = check(x)
+                assert torch.is_tensor(out) and out.dim() == 0 and out.dtype == Q.dtype and float(out) == 2.0
+            else:
+                with pytest.raises(ValueError, match="qpth_amd: lower (must be a tensor|has shape)"):
+                    check(x)
+    # the texts of lower's two refusals, as they were
+    with pytest.raises(ValueError, match=r"qpth_amd: lower must be a tensor of shape \(nBatch, 3\) or \(3,\)$"):
+        as_lower(2.0, Q, nineq, nBatch)
+    with pytest.raises(ValueError, match=r"qpth_amd: lower has shape \(\); expected \(nBatch, 3\) or \(3,\)$"):
+        as_lower(torch.tensor(2.0, dtype=torch.float64), Q, nineq, nBatch)
+    with pytest.raises(ValueError, match=r"qpth_amd: rho has shape \(2, 4\); expected \(nBatch, 3\), \(3,\) or \(\)$"):
+        as_rho(torch.ones(2, 4, dtype=torch.float64), Q, nineq, nBatch)
+
+
 def test_sharded_solves_refuse_what_cannot_be_sharded():
     """the same error on every rank, before any collective: a batch smaller than the world, nothing batched"""
     import torch
