@@ -155,7 +155,11 @@ int qpx_can_share_factors(int dtype, int n, int m, int q);
  * it can be bracketed by events on its own.  QPX_ERR_UNSUPPORTED when (dtype, n, m, q) is not served by that family. */
 int qpx_big_gemm_r(int dtype, int B, int n, int m, int q, void* factors, qpx_stream_t stream);
 
-/* pre_factor_kkt(Q, G, A) */
+/* pre_factor_kkt(Q, G, A).  status[i] = 0, or exactly QPX_ST_Q_NOT_SPD / QPX_ST_A_RANK for a QP whose factorisation broke
+ * down; the blobs and status words of the other QPs of the batch are those of a batch without it, bit for bit.  The failed
+ * QP's own blob: ALL ZEROS (every one of its qpx_factor_elems words) from the thread-grid / matrix-core kernels; from the
+ * large-QP family unspecified -- the launches behind the failed diagonal block still run on it -- but for the failure bit
+ * among its control words (BigCtrl: bcFail), which stops qpx_ipm on that QP.  (tests/prefac_checks.py pins all of it.) */
 int qpx_pre_factor(int dtype, int B, int n, int m, int q,
                    const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
                    void* factors, int32_t* status, qpx_stream_t stream);
