@@ -16,6 +16,7 @@
  *   qpx_backward_duals .... (no reference counterpart)            the same for a loss of (zhat, lam, nu): cotangents on the multipliers
  *   qpx_jvp ............... (no reference counterpart)            QPFunctionFn.jvp: forward mode, the adjoint of qpx_backward(_duals)
  *   qpx_ipm_warm .......... (no reference counterpart)            qpx_ipm entered at a previous solution's (lam, slacks)
+ *   qpx_ipm_range_warm .... (no reference counterpart)            qpx_ipm_range entered at a previous solution's (lam, slacks, lam_lo, slacks_lo)
  *   qpx_factor_solve_kkt_multi  (no reference counterpart)       factor_kkt once, solve_kkt for K right-hand sides per QP: Jacobians
  *   qpx_backward2 ......... (no reference counterpart)            the second-order pass: the gradient of <W, qpx_backward's gradients>
  *   qpx_pre_factor_soft ... (no reference counterpart)            qpx_pre_factor with a quadratic penalty on the violation of chosen rows of G z <= h
@@ -391,8 +392,27 @@ int qpx_centre(int dtype, int B, int n, int m, int q,
  * (exactly 0 on a one-sided row), which the caller forms from dz; dh, if given, receives their sum -v.  refine must be 0.
  * Served in float64 arithmetic by the loop and backward forms the default dispatch picks, nz+neq+nineq <= 208
  * (qpx_range_supported); QPX_F32, QPX_F32_WIDE, the large-QP family and forms reachable through the A/B knob alone:
- * QPX_ERR_UNSUPPORTED.  No warm start, no soft factors (qpx_pre_factor_soft) and no refinement in this role. */
+ * QPX_ERR_UNSUPPORTED.  No soft factors (qpx_pre_factor_soft) and no refinement in this role.
+ * qpx_ipm_range_warm: qpx_ipm_range entered at a WARM START -- its arguments, then lam0, s0, lam0_lo, s0_lo (B,m),
+ * dense, of dtype: lam, slack, lam_lo, slack_lo of a previous solution of a nearby batch; warm_floor, warm_used as in
+ * qpx_ipm_warm.  Per QP: lam0, s0 are looked at on EVERY row, lam0_lo, s0_lo only on the rows that are two-sided in THIS call
+ * (lower > -inf).  If all of those entries are finite the loop starts at zu = max(lam0, warm_floor), su = max(s0, warm_floor),
+ * and on the two-sided rows zl = max(lam0_lo, warm_floor), sl = max(s0_lo, warm_floor), with x = x0 - M^T (zu - zl) implied
+ * (dual- and equality-feasible for any such iterate); the start point is skipped and the passes begin at 0.  The lower
+ * entries of a one-sided row are never read: the 0 and +inf a previous solve wrote there do not send the QP cold.  A row that
+ * is two-sided now and carries 0 / +inf from a solve in which it was one-sided is not finite: that QP, as any QP with a NaN
+ * or an Inf among the entries looked at, starts exactly as in qpx_ipm_range.  All four arrays NULL IS qpx_ipm_range (which is
+ * this call with NULLs); some but not all of them given, or a warm_floor that is not finite or <= 0: QPX_ERR_ARG.
+ * Served exactly where qpx_ipm_range is (qpx_range_warm_supported == qpx_range_supported for every argument and knob);
+ * anything else is QPX_ERR_UNSUPPORTED, never a fall-through to a kernel without the role. */
 int qpx_range_supported(int dtype, int n, int m, int q);
+int qpx_range_warm_supported(int dtype, int n, int m, int q);
+int qpx_ipm_range_warm(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
+                       const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
+                       int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
+                       void* best_resid, void* trace, const void* lower, int64_t slo, const void* gt1, void* lam_lo,
+                       void* slack_lo, const void* lam0, const void* s0, const void* lam0_lo, const void* s0_lo,
+                       double warm_floor, int32_t* warm_used, qpx_stream_t stream);
 int qpx_ipm_range(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
                   const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
                   int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,

@@ -9,6 +9,6 @@ hand-written gfx950 HIP kernels (one QP per workgroup, KKT blocks in LDS).
 """
 from . import qp, sensitivity, solvers, util  # noqa: F401
 from .qp import QPFunction, QPSolvers  # noqa: F401
-from .kkt import SoftRange, WarmStart, set_stall_policy  # noqa: F401
+from .kkt import RangeWarmStart, SoftRange, WarmStart, set_stall_policy  # noqa: F401
 
 __version__ = "0.1.0"

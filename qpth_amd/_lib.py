@@ -70,6 +70,10 @@ _SIGNATURES = {
     "qpx_range_supported": (_i, [_i, _i, _i, _i]),
     "qpx_ipm_range": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d, _i, _i, _i,
                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "qpx_range_warm_supported": (_i, [_i, _i, _i, _i]),
+    "qpx_ipm_range_warm": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d, _i, _i, _i,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _d, _vp, _vp]),
     "qpx_backward_range": (_i, [_i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "qpx_elastic_supported": (_i, [_i, _i, _i, _i]),
@@ -247,11 +251,19 @@ class QpxLib:
 
     # -- two-sided rows lower <= G z <= h: the loop's and the backward's range role, float64
     def ipm_range(self, B, n, m, q, p, h, lower, gt1, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
-                  zhat, nu, lam, slack, lam_lo, slack_lo, iters, status, best_resid, trace=None):
-        """lower (B,m), (1,m) or (m,) (shared: batch stride 0), -inf = a one-sided row; gt1 (B,) = || G^T e || or None (0)"""
+                  zhat, nu, lam, slack, lam_lo, slack_lo, iters, status, best_resid, trace=None,
+                  warm=None, warm_floor=1e-2, warm_used=None):
+        """lower (B,m), (1,m) or (m,) (shared: batch stride 0), -inf = a one-sided row; gt1 (B,) = || G^T e || or None (0).
+        warm = (lam0, s0, lam0_lo, s0_lo), (B,m) dense: the warm start (qpx_ipm_range_warm); without it the call is
+        qpx_ipm_range itself, as before."""
         lp = Param(lower, 2)
         common = (B, n, m, q, p, h, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
                   zhat, nu, lam, slack, iters, status, best_resid, trace)
+        if warm is not None:
+            self._ipm_call(self.dll.qpx_ipm_range_warm, common,
+                           lp.ptr, lp.stride, _ptr(gt1), _ptr(lam_lo), _ptr(slack_lo),
+                           *[_ptr(w) for w in warm], float(warm_floor), _ptr(warm_used))
+            return
         self._ipm_call(self.dll.qpx_ipm_range, common,
                        lp.ptr, lp.stride, _ptr(gt1), _ptr(lam_lo), _ptr(slack_lo))
 

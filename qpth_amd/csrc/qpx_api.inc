@@ -915,11 +915,18 @@ int qpx_range_supported(int dtype, int n, int m, int q)
     return qpx::range_served(dtype, n, m, q, 1) && qpx::range_served(dtype, n, m, q, 1 << 20) ? 1 : 0;
 }
 
-int qpx_ipm_range(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
-                  const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
-                  int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
-                  void* best_resid, void* trace, const void* lower, int64_t slo, const void* gt1, void* lam_lo,
-                  void* slack_lo, qpx_stream_t stream)
+int qpx_range_warm_supported(int dtype, int n, int m, int q)
+{
+    // every form with the range role has the role's warm entry (IpmArgs::lam0, s0, lam0_lo, s0_lo)
+    return qpx_range_supported(dtype, n, m, q);
+}
+
+int qpx_ipm_range_warm(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
+                       const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
+                       int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
+                       void* best_resid, void* trace, const void* lower, int64_t slo, const void* gt1, void* lam_lo,
+                       void* slack_lo, const void* lam0, const void* s0, const void* lam0_lo, const void* s0_lo,
+                       double warm_floor, int32_t* warm_used, qpx_stream_t stream)
 {
     const int e = qpx::check_dims(dtype, B, n, m, q);
     if (e) return e;
@@ -927,13 +934,31 @@ int qpx_ipm_range(int dtype, int B, int n, int m, int q, const void* p, int64_t 
         (q > 0 && (!nu || !b)))
         return QPX_ERR_ARG;
     if (maxIter < 0 || stall_policy < 0 || stall_policy > 2 || slo < 0) return QPX_ERR_ARG;
+    const int given = (lam0 != nullptr) + (s0 != nullptr) + (lam0_lo != nullptr) + (s0_lo != nullptr);
+    if (given != 0 && given != 4) return QPX_ERR_ARG;
+    if (!(warm_floor > 0) || !(warm_floor < __builtin_huge_val())) return QPX_ERR_ARG;      // NaN, Inf, <= 0 (as qpx_ipm_warm)
     if (!qpx::range_served(dtype, n, m, q, B)) return QPX_ERR_UNSUPPORTED;
     qpx::IpmArgs<double> a{};
     qpx::ipm_common_args(a, B, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters,
                          status, best_resid, trace);
     a.lower = (const double*)lower; a.slo = slo; a.gt1 = (const double*)gt1;
     a.lam_lo = (double*)lam_lo; a.slack_lo = (double*)slack_lo;
+    if (given) {
+        a.lam0 = (const double*)lam0; a.s0 = (const double*)s0; a.lam0_lo = (const double*)lam0_lo; a.s0_lo = (const double*)s0_lo;
+        a.warm_floor = warm_floor; a.warm_used = warm_used;
+    }
     return qpx::api_ipm_range(a, stream, true);
+}
+
+int qpx_ipm_range(int dtype, int B, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
+                  const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
+                  int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
+                  void* best_resid, void* trace, const void* lower, int64_t slo, const void* gt1, void* lam_lo,
+                  void* slack_lo, qpx_stream_t stream)
+{
+    return qpx_ipm_range_warm(dtype, B, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam,
+                              slack, iters, status, best_resid, trace, lower, slo, gt1, lam_lo, slack_lo, nullptr, nullptr, nullptr, nullptr, 1e-2,
+                              nullptr, stream);
 }
 
 int qpx_backward_range(int dtype, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat, const void* lam,

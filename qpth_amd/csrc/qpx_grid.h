@@ -1869,12 +1869,20 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     }
     Mat::sync(b);
     // warm start (IpmArgs): this QP takes (lam0, s0) only if all 2 m entries are finite -- decided by the lead wave here,
-    // read by every wave behind the barrier that ends the prologue's products
+    // read by every wave behind the barrier that ends the prologue's products.  Range role: (lam0_lo, s0_lo) as well, on the
+    // rows that are two-sided in THIS call only (two_sided_ of h - lower: vH is not formed yet) -- a one-sided row's lower
+    // entries are never read (a previous solve wrote 0 and +inf there), and a row that is two-sided now and carries 0 / +inf
+    // from a solve in which it was one-sided sends its QP cold
     const In<T> l0g(a.lam0, (size_t)qp * m, io32), s0g(a.s0, (size_t)qp * m, io32);
+    const In<T> l0lg(kRange ? a.lam0_lo : nullptr, (size_t)qp * m, io32), s0lg(kRange ? a.s0_lo : nullptr, (size_t)qp * m, io32);
     if (a.lam0 && w0) {
         T ok = T(1);
-        for (int i = lane; i < m; i += kWave)
+        for (int i = lane; i < m; i += kWave) {
             if (!finite_(l0g[i]) || !finite_(s0g[i])) ok = T(0);
+            if constexpr (kRange) {
+                if (two_sided_(hg[i] - lwg[i]) && (!finite_(l0lg[i]) || !finite_(s0lg[i]))) ok = T(0);
+            }
+        }
         ok = wave_min(b, ok);
         if (lane == 0) ctrl[kWarm] = ok > T(0);
     }
@@ -2022,6 +2030,9 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     // and nu = nu0 - W^T z are dual- and equality-feasible by construction, so pass -1 (the start point: one factorisation and
     // one solve) is not needed and the passes begin at 0.  R 1 is formed in pass -1 only: zeroed, tau sigma_z R 1 must not
     // meet what LDS held.  The best iterate is taken at pass 0 as ever; it is set here for a breakdown inside that pass.
+    // Range role: both sides, zl = max(lam0_lo, f), sl = max(s0_lo, f) on the two-sided rows (0 and +inf elsewhere), z' = zu - zl,
+    // and the reciprocals and the diagonal 1/(wu + wl) with the iterate (range_recips), as every block that leaves an iterate
+    // forms them: pass 0 reads vD at its top (vH[i], vD[i] were written by this thread in the loop above).
     const bool warm = !kElastic && !kSoft && a.lam0 && ctrl[kWarm];
     if (warm) {
         const T fl = a.warm_floor;
@@ -2030,7 +2041,16 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
                 const T zk = max2_(fl, l0g[i]), sk = max2_(fl, s0g[i]);
                 vZ[i] = zk; vS[i] = sk;
                 vBZ[i] = zk; vBS[i] = sk;
-                vA[i] = zk;
+                if constexpr (kRange) {
+                    const bool f = two_sided_(vH[i]);
+                    const T zl = f ? max2_(fl, l0lg[i]) : T(0), sl = f ? max2_(fl, s0lg[i]) : Lim<T>::inf();
+                    vZL[i] = zl; vSL[i] = sl;
+                    vBZL[i] = zl; vBSL[i] = sl;
+                    vA[i] = zk - zl;
+                    range_recips(f, i, zk, sk, zl, sl, vRZ, vRS, vRZL, vRSL, vD);
+                } else {
+                    vA[i] = zk;
+                }
             } else {
                 vA[i] = T(0);
             }

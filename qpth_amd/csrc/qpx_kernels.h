@@ -189,6 +189,10 @@ template <class T> struct IpmArgs {
     const T *gamma_lo = nullptr, *rho_lo = nullptr;
     long long sgamma_lo = 0, srho_lo = 0;
     T *lam_t = nullptr, *slack_t = nullptr, *lam_tl = nullptr, *slack_tl = nullptr, *tviol_lo = nullptr;
+    // warm start of the range role (qpx_ipm_range_warm): the lower side's lam0_lo, s0_lo (B,m) dense beside lam0, s0 above.  A
+    // QP is warm if lam0, s0 are finite on every row and lam0_lo, s0_lo on every row that is two-sided in THIS call (the
+    // entries of a one-sided row are never read: a previous solve left 0 and +inf there); any other QP starts cold
+    const T *lam0_lo = nullptr, *s0_lo = nullptr;
 };
 
 template <class T> struct KktArgs {

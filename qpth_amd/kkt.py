@@ -83,6 +83,44 @@ class WarmStart:
         return (self.lam, self.slacks) if self.matches(B, m, dtype, device) else None
 
 
+class RangeWarmStart:
+    """WarmStart for two-sided rows, lower <= G z <= h: the (lam, slacks, lam_lo, slacks_lo) of the previous solve of a batch
+    (QPFunction(warm_start=rws)(Q, p, G, h, A, b, lower=l), sensitivity.solve(..., lower=l, warm_start=rws)):
+
+        rws = qpth_amd.RangeWarmStart()
+        for step in range(steps):
+            z = QPFunction(warm_start=rws)(Q, p, G, h, A, b, lower=l)      # first call cold, every later one warm
+
+    A type of its own on purpose: a holder filled by a one-sided solve has nothing for the lower side, so handing a
+    WarmStart to a call with `lower` (or this one to a call without) is an error, not a silent cold start.  `used`, `floor`,
+    `clear()` and the rule for a holder of another (B, nineq), dtype or device are WarmStart's.  Which rows are two-sided may
+    change between calls: a row that was one-sided in the previous solve and is two-sided now carries 0 / +inf on its lower
+    side, and that QP starts cold (`used` says so); the other way round its lower entries are simply not read."""
+
+    def __init__(self, floor=1e-2):
+        if not (floor > 0 and floor < float("inf")):
+            raise ValueError("qpth_amd: RangeWarmStart floor must be positive and finite, got %r" % (floor,))
+        self.floor = float(floor)
+        self.clear()
+
+    def clear(self):
+        self.lam = self.slacks = self.lam_lo = self.slacks_lo = self.used = None
+
+    def matches(self, B, m, dtype, device):
+        return all(X is not None and tuple(X.shape) == (B, m) and X.dtype == dtype and X.device == device
+                   for X in (self.lam, self.slacks, self.lam_lo, self.slacks_lo))
+
+    def take(self, res):
+        """keep what a forward produced (KKTFactors.ipm_range's result)"""
+        self.lam, self.slacks, self.lam_lo, self.slacks_lo = (res.lam.detach(), res.slacks.detach(), res.lam_lo.detach(),
+                                                              res.slacks_lo.detach())
+        self.used = res.warm_used
+
+    def quad(self, B, m, dtype, device):
+        """(lam, slacks, lam_lo, slacks_lo) for KKTFactors.ipm_range(warm=...), or None when the holder is empty or of another batch"""
+        return (self.lam, self.slacks, self.lam_lo, self.slacks_lo) if self.matches(B, m, dtype, device) else None
+
+
 def _batch_of(*params3):
     for X in params3:
         if X is not None and X.nelement() > 0 and X.dim() == 3:
@@ -569,24 +607,41 @@ a non-zero diagonal.
         g = torch.matmul(e.unsqueeze(-2), G).squeeze(-2)
         return torch.linalg.vector_norm(g, dim=-1).expand(self.B).contiguous()
 
-    def ipm_range(self, p, h, lower, b, eps=1e-12, maxIter=20, notImprovedLim=3, stall_policy=None, want_trace=False):
+    def ipm_range(self, p, h, lower, b, eps=1e-12, maxIter=20, notImprovedLim=3, stall_policy=None, want_trace=False,
+                  warm=None, warm_floor=1e-2):
         """The IPM loop for  lower <= G z <= h  in nineq rows (qpx_ipm_range): the iterates of ipm() on the doubled QP
         [G; -G_F] z <= [h; -lower_F], one launch, no host sync.  lower (B, nineq), (1, nineq) or (nineq,); -inf = a one-sided
         row.  The result has lam, slacks of the rows G z <= h and lam_lo, slacks_lo of lower <= G z (0 and +inf on a one-sided
-        row).  A lower entry that is NaN, +inf or not below its h: QPX_ST_NONFINITE in `status` (raise_on_failure)."""
+        row).  A lower entry that is NaN, +inf or not below its h: QPX_ST_NONFINITE in `status` (raise_on_failure).
+        warm = (lam0, s0, lam0_lo, s0_lo), each (B, nineq): the loop starts at both sides' max(., warm_floor) instead of the
+        start point (qpx_ipm_range_warm), QP by QP where lam0, s0 are finite on every row and lam0_lo, s0_lo on
+        the rows that are two-sided in this call (a one-sided row's lower entries are not read).  `result.warm_used`, int32
+        (B,): 1 where it did."""
         self._require_role(*self._RANGE)
         B, n, m, q = self.B, self.n, self.m, self.q
+        kw = {}
+        if warm is not None:
+            if len(warm) != 4:
+                raise ValueError("qpth_amd: ipm_range takes warm = (lam0, s0, lam0_lo, s0_lo), got %d entries" % len(warm))
+            if not (warm_floor > 0 and warm_floor < float("inf")):
+                raise ValueError("qpth_amd: warm_floor must be positive and finite, got %r" % (warm_floor,))
+            names = ("warm[0] (lam0)", "warm[1] (s0)", "warm[2] (lam0_lo)", "warm[3] (s0_lo)")
+            kw = dict(warm=[self._vec(X, m, name) for X, name in zip(warm, names)], warm_floor=warm_floor)
+            if any(X is None for X in kw["warm"]):
+                raise ValueError("qpth_amd: ipm_range(warm=...) needs all four of lam0, s0, lam0_lo, s0_lo")
         self._check_ph(p, h)
         self._check(lower, m, "lower")
         self._check_b(b)
         r = self._new_result(maxIter, want_trace, ("lam_lo", "slacks_lo"))
+        if warm is not None:
+            r._warm_used = kw["warm_used"] = torch.empty(B, dtype=torch.int32, device=self.device)    # the kernel writes every QP's word
         lo, hd = lower.detach(), h.detach()
         self._stage_entry_checks(r, ("lower must be below h",), ~(lo < hd))
         gt1 = self.gt1_of(lo, hd)
         with self._knob():
             self.lib.ipm_range(B, n, m, q, p, h, lower, gt1, b if q else None, self.blob, self.sfac, eps, maxIter,
                                notImprovedLim, self._stall(stall_policy), r.zhat, r.nu if q else None, r.lam, r.slacks, r.lam_lo,
-                               r.slacks_lo, r.iters, r.status, r.best_resid, r.trace)
+                               r.slacks_lo, r.iters, r.status, r.best_resid, r.trace, **kw)
         return r
 
     def backward_range(self, zhat, lam, slacks, lam_lo, slacks_lo, nu, dl_dz, want=(True,) * 7, shared=(False,) * 7):

@@ -19,6 +19,8 @@ QPFunction(...)(Q, p, G, h, A, b, kappa=kappa) returns the point of the CENTRAL 
 log-barrier smoothing of the QP, C-infinity in all parameters and in kappa; one more launch in the forward (qpx_centre).
 QPFunction(...)(Q, p, G, h, A, b, lower=l) solves  l <= Gz <= h  in nineq rows -- not [G; -G] z <= [h; -l] in 2 nineq --, differentiable
 in l as well: the loop's and the backward's range role, the same number of launches (qpx_ipm_range).
+QPFunction(warm_start=rws)(Q, p, G, h, A, b, lower=l) with a qpth_amd.RangeWarmStart starts that loop at the previous call's
+(lam, slacks, lam_lo, slacks_lo) (qpx_ipm_range_warm).
 QPFunction(...)(Q, p, G, h, A, b, rho, l1=gamma) makes the rows ELASTIC: the exact penalty gamma't + 1/2 t'diag(rho)t on the violations
 t >= 0 of Gz <= h + t, in nineq rows and nz variables -- not the augmented dense QP in (z, t) --, differentiable in gamma and rho:
 the loop's elastic role on the hard QP's factors, the backward as it stands (qpx_ipm_elastic).
@@ -34,7 +36,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .kkt import KKTFactors, SoftRange, _reduce_like, _rows, as_kappa, as_l1, as_lower, as_rho
+from .kkt import KKTFactors, RangeWarmStart, SoftRange, _reduce_like, _rows, as_kappa, as_l1, as_lower, as_rho
 from .solvers.pdipm import batch as pdipm_b
 from .util import expandParam, extract_nBatch
 
@@ -129,6 +131,8 @@ _WITH_LOWER = " together with lower (two-sided rows) is not served"
 _IN_HOLDER = " together with %s is not served: the SoftRange holder carries the bounds and penalties"
 _DUALS = " with duals=True is not served (the multipliers are no outputs of this node)"
 _WARM = " with warm_start is not served"
+_WARM_ONE_SIDED = (" with warm_start=WarmStart() is not served: that holder has nothing for the lower side (pass a "
+                   "qpth_amd.RangeWarmStart to warm-start this call)")
 _REFINE = " with refine=%(refine)d is not served: pass refine=0 or refine=None"
 _SOLVER = " is served by solver=QPSolvers.PDIPM_BATCHED only"
 _ROW_KINDS = {
@@ -141,7 +145,7 @@ _ROW_KINDS = {
     "lower": ("qpth_amd: lower (two-sided rows)", "; write the rows as [G; -G] z <= [h; -lower] instead", "range role",
               "qpx_range_supported",
               (("rho", _WITH_RHO), ("kappa", _WITH_KAPPA), ("solver", _SOLVER), ("refine", _REFINE), ("duals", _DUALS),
-               ("warm_start", _WARM))),
+               ("warm_start", _WARM_ONE_SIDED))),
     "kappa": ("qpth_amd: kappa (the barrier-smoothed QP)", "", "centring kernel", "qpx_centre_supported",
               (("rho", _WITH_RHO + ": the centring steps evaluate the residuals of the hard QP"), ("solver", _SOLVER),
                ("refine", " with refine=%(refine)d: the centring launch already iterates on the residuals of the caller's data; "
@@ -214,9 +218,15 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
       so lower = -inf everywhere is the six-input QP.  A seventh differentiable input in reverse mode (d loss / d lower is
       exactly 0 on a one-sided row); a shared lower gets the `.mean(0)` convention.  An entry that is NaN, +inf or not below
       its h raises ValueError("lower must be below h") from the forward.  float64 inputs at sizes the thread-grid / tile
-      kernels serve (nz+neq+nineq <= 208) only; not together with rho, kappa, refine > 0, duals=True, warm_start, float32
+      kernels serve (nz+neq+nineq <= 208) only; not together with rho, kappa, refine > 0, duals=True, a plain WarmStart, float32
       inputs or solver=QPSolvers.CVXPY: each a ValueError from the call that names the doubled call as the way out.  Forward
       mode and second derivatives are not served: RuntimeError.  lower=None is the call as before: the same nodes and launches.
+      warm_start=qpth_amd.RangeWarmStart(), the SAME object on every step: the first call is cold, every later
+      one enters the loop at the previous call's (lam, slacks, lam_lo, slacks_lo), floored at its `floor`; `used`, a holder of
+      another batch and `clear()` as for WarmStart below.  A QP in which a row that was one-sided in the previous call is
+      two-sided now starts cold.  The solution and the backward are those of the cold call to the solver's tolerance.  That
+      holder without lower, or with rho, kappa, l1 or soft_range: ValueError.  After a LARGE step (0.1 on the box of the
+      headline shape) a warm start can cost more passes than the start point, or stall: clear the holder then.
     kappa: the barrier-smoothed QP.  The call returns the point of the central path
           Q z + p + G'lam + A'nu = 0,  G z + s = h,  A z = b,  s_i lam_i = kappa_i   (s, lam > 0),
       the minimiser of 1/2 z'Qz + p'z - sum_i kappa_i log(h_i - g_i'z) s.t. Az = b, instead of the QP's solution: smooth in all
@@ -520,8 +530,13 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
         """the node of two-sided rows: lower, the seventh differentiable input, behind the six parameters"""
         @staticmethod
         def forward(ctx, Q_, p_, G_, h_, A_, b_, lower_):
-            _, p, h, b, fac = _hard_factors(ctx, (Q_, p_, G_, h_, A_, b_), (lower_,))
-            res = fac.ipm_range(p, h, lower_.detach(), b, eps, maxIter, notImprovedLim, want_trace=(verbose == 1))
+            nBatch, p, h, b, fac = _hard_factors(ctx, (Q_, p_, G_, h_, A_, b_), (lower_,))
+            # (a RangeWarmStart: _gate let it through; the first call and a holder of another batch are cold)
+            warm = warm_start.quad(nBatch, G_.size(-2), Q_.dtype, Q_.device) if warm_start is not None else None
+            res = fac.ipm_range(p, h, lower_.detach(), b, eps, maxIter, notImprovedLim, want_trace=(verbose == 1), warm=warm,
+                                warm_floor=warm_start.floor if warm is not None else 1e-2)
+            if warm_start is not None:
+                warm_start.take(res)
             _loop_epilogue(fac, res, check_Q_spd, verbose)
             ctx.fac = fac
             ctx.nus, ctx.lams, ctx.slacks, ctx.lams_lo, ctx.slacks_lo = res.nu, res.lam, res.slacks, res.lam_lo, res.slacks_lo
@@ -633,7 +648,9 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             return _without_A_b(grads[:6], ctx.neq) + five
 
     # the options of this QPFunction(...) that a row kind may refuse (_ROW_KINDS): is each one set?
-    option_set = {"duals": bool(duals), "warm_start": warm_start is not None, "refine": refine is not None and int(refine) > 0,
+    # (a RangeWarmStart is the range role's own holder: apply() has refused it everywhere else, the role does not refuse it)
+    range_ws = isinstance(warm_start, RangeWarmStart)
+    option_set = {"duals": bool(duals), "warm_start": warm_start is not None and not range_ws, "refine": refine is not None and int(refine) > 0,
                   "solver": solver != QPSolvers.PDIPM_BATCHED}
 
     def _gate(kind, Q, G, A, **given):
@@ -653,6 +670,12 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
 
     def apply(Q, p, G, h, A, b, rho=None, kappa=None, lower=None, l1=None, soft_range=None):
         nineq = G.size(-2)
+        if range_ws:
+            with_ = [name for name, x in (("rho", rho), ("kappa", kappa), ("l1", l1), ("soft_range", soft_range)) if x is not None]
+            if lower is None or with_:
+                raise ValueError("qpth_amd: warm_start=RangeWarmStart() is the holder of two-sided rows (lower=) alone; got a call %s.  "
+                                 "Pass a qpth_amd.WarmStart to the hard QP's call"
+                                 % ("with " + ", ".join(with_) if with_ else "without lower"))
         if soft_range is not None:
             if not isinstance(soft_range, SoftRange):
                 raise ValueError(_ROW_KINDS["soft_range"][0] + " must be a qpth_amd.SoftRange(lower, l1, rho, l1_lower=None, "
