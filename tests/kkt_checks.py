@@ -123,6 +123,7 @@ measured = {}        # "check/case/d" -> worst figure seen (scripts/check_kkt.py
 gates = {}           # the same keys -> the gate the figure was held to
 reference_side = {}  # what the gates rest on: the unrefined float64 / the float32 dense solve against the refined reference
 k1_bitwise = {}      # case -> did K = 1 of the multi solve equal the single solve bit for bit
+rule_decided = {}    # case/d -> did 100 x the unrefined dense solve's error exceed TOL (only the cases that ask for the rule)
 
 
 # ---------------------------------------------------------------- the reference
@@ -274,9 +275,10 @@ class Case:
     """One batch and one d: the data, the random inputs of every check and, made once and shared by every form, their
     references"""
 
-    def __init__(self, env, shape, B, kind, dtype, prob):
+    def __init__(self, env, shape, B, kind, dtype, prob, cond_rule=False):
         n, m, q = shape
         self.shape, self.B, self.kind, self.dtype, self.prob, self.dev = tuple(shape), B, kind, dtype, prob, env.dev
+        self.cond_rule = cond_rule
         self.arrs = problem(shape, B, dtype, prob)
         Q, p, G, h, A, b = self.arrs
         r = rng(shape, 1 if kind == "bwd" else 2)
@@ -408,9 +410,9 @@ def multi_ks():
     return (1, RB + 1, 2 * RB + 3)          # one, two and three blocks, the last ones ragged
 
 
-def case(env, shape, kind, B=B3, dtype="f64", prob="prof"):
-    key = ("case", env.dev.type, tuple(shape), B, kind, dtype, prob)
-    return cached(key, lambda: Case(env, shape, B, kind, dtype, prob))
+def case(env, shape, kind, B=B3, dtype="f64", prob="prof", cond_rule=False):
+    key = ("case", env.dev.type, tuple(shape), B, kind, dtype, prob, cond_rule)
+    return cached(key, lambda: Case(env, shape, B, kind, dtype, prob, cond_rule))
 
 
 def factors(env, c, form, shared=False):
@@ -430,8 +432,14 @@ def code_of(fac):
 
 
 def tol_of(c):
-    """the gate of the case's dtype: TOL, TOL_WIDE, or for QPX_F32 max(1e-3, 100 x the float32 dense solve's error)"""
+    """the gate of the case's dtype: TOL, TOL_WIDE, or for QPX_F32 max(1e-3, 100 x the float32 dense solve's error).  A float64
+    case made with cond_rule=True (tests/big_checks.py: orders up to 1 088) takes the conditioning rule, max(TOL, 100 x the
+    unrefined float64 dense solve against the refined reference), and records in rule_decided whether the second term decided"""
     if c.dtype == "f64":
+        if c.cond_rule:
+            side = 100.0 * c.reference_side()["dense64"]
+            rule_decided["%s/B%d/%s/%s" % (tag(c.shape), c.B, c.prob, c.kind)] = bool(side > TOL)
+            return max(TOL, side)
         return TOL
     if c.dtype == "wide":
         return TOL_WIDE
@@ -615,10 +623,10 @@ def checks_1_to_4(env, c, form, fac, name):
     return out, g
 
 
-def check_solve(env, shape, form=0):
+def check_solve(env, shape, form=0, B=B3, prob="prof", kinds=DKINDS, cond_rule=False):
     g = Gate()
-    for kind in DKINDS:
-        c = case(env, shape, kind)
+    for kind in kinds:
+        c = case(env, shape, kind, B, "f64", prob, cond_rule)
         with env.run(form):
             fac = factors(env, c, form)
             gate_solve(g, c, run_solve(fac, c), c.name(form))
@@ -627,10 +635,10 @@ def check_solve(env, shape, form=0):
     g.done()
 
 
-def check_backward(env, shape, form=0):
+def check_backward(env, shape, form=0, B=B3, prob="prof", kinds=DKINDS, cond_rule=False):
     g = Gate()
-    for kind in DKINDS:
-        c = case(env, shape, kind)
+    for kind in kinds:
+        c = case(env, shape, kind, B, "f64", prob, cond_rule)
         with env.run(form):
             fac = factors(env, c, form)
             gate_backward(g, c, run_backward(fac, c), c.name(form))
@@ -638,10 +646,10 @@ def check_backward(env, shape, form=0):
     g.done()
 
 
-def check_jvp(env, shape, form=0):
+def check_jvp(env, shape, form=0, B=B3, prob="prof", kinds=DKINDS, cond_rule=False):
     g = Gate()
-    for kind in DKINDS:
-        c = case(env, shape, kind)
+    for kind in kinds:
+        c = case(env, shape, kind, B, "f64", prob, cond_rule)
         with env.run(form):
             fac = factors(env, c, form)
             gate_jvp(g, c, run_jvp(fac, c), c.name(form), run_backward(fac, c)["duals"])
@@ -649,11 +657,11 @@ def check_jvp(env, shape, form=0):
     g.done()
 
 
-def check_multi(env, shape, form=0):
+def check_multi(env, shape, form=0, B=B3, prob="prof", kinds=DKINDS, cond_rule=False):
     """returns False where the form declines the role (and the query was asserted to say so)"""
     g = Gate()
-    for kind in DKINDS:
-        c = case(env, shape, kind)
+    for kind in kinds:
+        c = case(env, shape, kind, B, "f64", prob, cond_rule)
         with env.run(form):
             fac = factors(env, c, form)
             assert multi_supported(fac) == multi_expected(shape, form), (shape, form, "qpx_multi_supported")
@@ -681,9 +689,9 @@ def check_multi_k1(env, shape, form=0, B=B3, prob="prof"):
     return True
 
 
-def check_backward2(env, shape, form=0):
+def check_backward2(env, shape, form=0, B=B3, prob="prof", kind="bwd"):
     """returns False where the form declines the role (and the query was asserted to say so)"""
-    c = case(env, shape, "bwd")
+    c = case(env, shape, kind, B, "f64", prob)
     g = Gate()
     with env.run(form):
         fac = factors(env, c, form)
@@ -737,9 +745,9 @@ def check_shared_factors(env, shape):
     g.done()
 
 
-def check_f32_grid(env, shape):
-    """QPX_F32 tensors on the thread-grid kernels, the "mid" d"""
-    c = case(env, shape, "mid", dtype="f32", prob="dense")
+def check_f32_grid(env, shape, B=B3):
+    """QPX_F32 tensors on the thread-grid kernels (B=: tests/big_checks.py, the large-QP family's), the "mid" d"""
+    c = case(env, shape, "mid", B=B, dtype="f32", prob="dense")
     with env.run(0):
         fac = factors(env, c, 0)
         assert not fac.wide and fac.blob.dtype == torch.float32

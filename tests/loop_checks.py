@@ -108,8 +108,11 @@ def tag(shape, form=0):
     return "%dx%dx%d/%d" % (tuple(shape) + (form,))
 
 
-def batch_of(shape, form):
-    """three QPs wherever QPs may share a workgroup or a launch's grid; the large-QP family works on each QP by itself"""
+def batch_of(shape, form, B=None):
+    """three QPs wherever QPs may share a workgroup or a launch's grid; the large-QP family works on each QP by itself.
+    B: the caller's own batch size (tests/big_checks.py)"""
+    if B is not None:
+        return B
     return 2 if (form == 3 or tuple(shape) == BIG) else 3
 
 
@@ -125,9 +128,10 @@ def fig(a, ref):
 
 
 @functools.lru_cache(maxsize=None)
-def problem(shape, B, dtype="f64"):
-    """prof_qp in float64; "f32": the same data rounded to float32 (returned as float64 arrays: what the oracle is given)"""
-    arrs = problems.prof_qp(B, *shape, seed=SEED)
+def problem(shape, B, dtype="f64", prob="prof"):
+    """prof_qp in float64 (prob = "dense": problems.random_dense_qp); "f32": the same data rounded to float32 (returned as
+    float64 arrays: what the oracle is given)"""
+    arrs = (problems.random_dense_qp if prob == "dense" else problems.prof_qp)(B, *shape, seed=SEED)
     if dtype == "f32":
         arrs = tuple(np.asarray(np.asarray(x, np.float32), np.float64) for x in arrs)
     for x in arrs:
@@ -136,28 +140,28 @@ def problem(shape, B, dtype="f64"):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle(shape, B, i, eps, maxIter, want_trace=False, dtype="f64"):
+def oracle(shape, B, i, eps, maxIter, want_trace=False, dtype="f64", prob="prof"):
     """QP i of the batch ALONE (one thread: microseconds of work each), the loop of batch.py:47-207 with the per-QP stop rule
     and the reference's stall counter: (x, y, z, s, info).  Computed once per (problem, setting), shared by every form."""
     from oracle import qp_oracle as orc
-    Q, p, G, h, A, b = problem(shape, B, dtype)
+    Q, p, G, h, A, b = problem(shape, B, dtype, prob)
     q = shape[2]
     o = orc.OracleQP(Q[i:i + 1], p[i:i + 1], G[i:i + 1], h[i:i + 1], A[i:i + 1] if q else None, b[i:i + 1] if q else None,
                      nthreads=1)
     return o.forward(eps, maxIter, 3, True, 1, want_trace=want_trace)
 
 
-def factors(env, shape, B, dtype="f64"):
+def factors(env, shape, B, dtype="f64", prob="prof"):
     """(fac, p, h, b) on env.dev; call inside env.run(form)"""
     from qpth_amd.kkt import KKTFactors
     td = torch.float64 if dtype == "f64" else torch.float32
     Q, p, G, h, A, b = [torch.tensor(np.asarray(x), dtype=td, device=env.dev) if np.size(x) else
-                        torch.empty(0, dtype=td, device=env.dev) for x in problem(shape, B, dtype)]
+                        torch.empty(0, dtype=td, device=env.dev) for x in problem(shape, B, dtype, prob)]
     return KKTFactors.build(Q, G, A, B, wide=(dtype == "f32")), p, h, b
 
 
 # ---------------------------------------------------------------- 1. the iterates after k iterations
-def compare_iterates(res, shape, B, k, dtype="f64", qps=None):
+def compare_iterates(res, shape, B, k, dtype="f64", qps=None, prob="prof"):
     """the launch's best iterate against the oracle capped at the same k, over the chosen QPs: the worst figure of the
     iterates, and best_resid's as the trace's numbers are compared in check 2 (it is their sum): |a - ref| / max(1, |ref|), and
     the plain relative difference where |ref| >= 1e-3; below that the plain relative difference is only kept for the record"""
@@ -166,7 +170,7 @@ def compare_iterates(res, shape, B, k, dtype="f64", qps=None):
     nu = host(res.nu) if q else None
     out = {"iterates": 0.0, "best": 0.0, "best_rel": 0.0, "best_rel_small": 0.0}
     for i in (range(B) if qps is None else qps):
-        x, y, zr, sr, info = oracle(shape, B, i, 1e-12, k, False, dtype)
+        x, y, zr, sr, info = oracle(shape, B, i, 1e-12, k, False, dtype, prob)
         assert it[i] == info["iters"][0], (i, k, it, info["iters"])
         f = [fig(z[i], x[0]), fig(lam[i], zr[0]), fig(s[i], sr[0])]
         if q:
@@ -183,15 +187,15 @@ def compare_iterates(res, shape, B, k, dtype="f64", qps=None):
 _runs = {}           # (device type, shape, form) -> the capped launches' figures
 
 
-def iterates_run(env, shape, form):
-    key = (env.dev.type, tuple(shape), form)
+def iterates_run(env, shape, form, ks=KS, B=None, prob="prof"):
+    key = (env.dev.type, tuple(shape), form) + (() if (ks, B, prob) == (KS, None, "prof") else (tuple(ks), B, prob))
     if key not in _runs:
-        B = batch_of(shape, form)
+        B = batch_of(shape, form, B)
         out = {}
         with env.run(form):
-            fac, p, h, b = factors(env, shape, B)
-            for k in KS:
-                out[k] = compare_iterates(fac.ipm(p, h, b, eps=1e-12, maxIter=k, stall_policy=1), shape, B, k)
+            fac, p, h, b = factors(env, shape, B, prob=prob)
+            for k in ks:
+                out[k] = compare_iterates(fac.ipm(p, h, b, eps=1e-12, maxIter=k, stall_policy=1), shape, B, k, prob=prob)
         _runs[key] = out
     return _runs[key]
 
@@ -206,8 +210,8 @@ def gate_iterates(name, out, tol=TOL):
     assert max(worst["iterates"], worst["best"], worst["best_rel"]) <= tol, out
 
 
-def check_iterates_after_k(env, shape, form=0):
-    gate_iterates(tag(shape, form), iterates_run(env, shape, form))
+def check_iterates_after_k(env, shape, form=0, ks=KS, B=None, prob="prof"):
+    gate_iterates(tag(shape, form), iterates_run(env, shape, form, ks, B, prob))
 
 
 def one_wave_run(env):
@@ -237,14 +241,14 @@ def check_one_wave_beyond_512(env):
 
 
 # ---------------------------------------------------------------- 2. iteration counts and the trace at eps = 1e-8
-def compare_trace(res, shape, B, maxIter, qps=None):
+def compare_trace(res, shape, B, maxIter, qps=None, prob="prof"):
     """`iters` equal; trace[:iters] against the oracle's: (worst |a - ref| / max(1, |ref|), worst relative difference over
     |ref| >= 1e-3); the buffer's rows from `iters` on untouched"""
     it, tr = host(res.iters), host(res.trace)
     assert tr.shape == (maxIter, B, 3)
     worst, rel = 0.0, 0.0
     for i in (range(B) if qps is None else qps):
-        info = oracle(shape, B, i, 1e-8, maxIter, True)[4]
+        info = oracle(shape, B, i, 1e-8, maxIter, True, "f64", prob)[4]
         assert it[i] == info["iters"][0], (i, it, info["iters"])
         mine, ref = tr[:it[i], i], info["trace"][:it[i]]
         assert np.isfinite(mine).all() and np.isfinite(ref).all()
@@ -256,17 +260,17 @@ def compare_trace(res, shape, B, maxIter, qps=None):
     return worst, rel
 
 
-def run_to_1e8(env, shape, form):
+def run_to_1e8(env, shape, form, B=None, prob="prof"):
     """the run of checks 2 and 3: (fac, p, h, b, B, result); call inside env.run(form)"""
-    B = batch_of(shape, form)
-    fac, p, h, b = factors(env, shape, B)
+    B = batch_of(shape, form, B)
+    fac, p, h, b = factors(env, shape, B, prob=prob)
     return fac, p, h, b, B, fac.ipm(p, h, b, eps=1e-8, maxIter=20, stall_policy=1, want_trace=True)
 
 
-def check_counts_and_trace(env, shape, form=0):
+def check_counts_and_trace(env, shape, form=0, B=None, prob="prof"):
     with env.run(form):
-        fac, p, h, b, B, res = run_to_1e8(env, shape, form)
-    worst, rel = compare_trace(res, shape, B, 20)
+        fac, p, h, b, B, res = run_to_1e8(env, shape, form, B, prob)
+    worst, rel = compare_trace(res, shape, B, 20, prob=prob)
     note("trace/" + tag(shape, form), worst)
     note("trace_rel/" + tag(shape, form), rel)
     assert worst <= TOL, worst
@@ -274,10 +278,10 @@ def check_counts_and_trace(env, shape, form=0):
 
 
 # ---------------------------------------------------------------- 3. the best iterate's bookkeeping
-def check_best_iterate(env, shape, form=0):
+def check_best_iterate(env, shape, form=0, B=None, prob="prof"):
     m = shape[1]
     with env.run(form):
-        fac, p, h, b, B, res = run_to_1e8(env, shape, form)
+        fac, p, h, b, B, res = run_to_1e8(env, shape, form, B, prob)
         it, tr, best = host(res.iters), host(res.trace), host(res.best_resid)
         outs = [host(x) for x in (res.zhat, res.lam, res.slacks)]
         worst = 0.0
@@ -293,19 +297,19 @@ def check_best_iterate(env, shape, form=0):
 
 
 # ---------------------------------------------------------------- 4. stall_policy = 0; the counts at eps = 1e-12
-def check_no_stall_counter(env, shape, form=0, maxIter=20):
+def check_no_stall_counter(env, shape, form=0, maxIter=20, B=None, prob="prof"):
     """Without the stall counter and with the stop rule's best_resid < eps out of reach the loop runs maxIter passes exactly,
     says QPX_ST_MAXITER for every QP and returns finite numbers.  Out of reach is eps = 0: at eps = 1e-30 it is not -- on small
     QPs both residual norms come out as exact zeros and nineq mu falls by 1e3 per pass, so best_resid does get below 1e-30
     (at (1, 1, 0) after 11 or 12 passes, in oracle/qp_oracle too).  At eps = 1e-30 therefore: a QP that stopped early, or at
     maxIter without the bit, is one whose best_resid is below 1e-30 -- nothing else may end the loop."""
     from qpth_amd import _lib
-    B = batch_of(shape, form)
+    B = batch_of(shape, form, B)
     with env.run(form):
-        fac, p, h, b = factors(env, shape, B)
+        fac, p, h, b = factors(env, shape, B, prob=prob)
         res = fac.ipm(p, h, b, eps=0.0, maxIter=maxIter, stall_policy=0)
         # (status words accumulate on the factors: fresh ones for the second launch)
-        fac30, p, h, b = factors(env, shape, B)
+        fac30, p, h, b = factors(env, shape, B, prob=prob)
         r30 = fac30.ipm(p, h, b, eps=1e-30, maxIter=maxIter, stall_policy=0)
     assert np.array_equal(host(res.iters), np.full(B, maxIter)), host(res.iters)
     assert (host(res.status) & _lib.ST_MAXITER).all(), host(res.status)
@@ -330,8 +334,8 @@ def record_counts(env, shape):
 
 
 # ---------------------------------------------------------------- 5. float32 tensors in float64 arithmetic
-def check_wide_iterates(env, shape):
-    B = batch_of(shape, 0)
+def check_wide_iterates(env, shape, B=None):
+    B = batch_of(shape, 0, B)
     worst = {}
     with env.run(0):
         fac, p, h, b = factors(env, shape, B, "f32")

@@ -189,7 +189,10 @@ def cached(key, make):
     return _cache[key]
 
 
-def batch_of(shape, knob):
+def batch_of(shape, knob, B=None):
+    """B: the caller's own batch size (tests/big_checks.py)"""
+    if B is not None:
+        return B
     return 2 if (knob == BIGK or tuple(shape) == tuple(BIG)) else B3
 
 
@@ -261,12 +264,12 @@ class Ref:
     """One batch's references (made once, shared by every knob and by both runners): per QP the arrays of the family, the
     plain float64 (float32) route's figure per array, the residual of the refined inverse"""
 
-    def __init__(self, shape, B, dtype, prob, big):
+    def __init__(self, shape, B, dtype, prob, big, qps=None):
         self.shape, self.B, self.big = tuple(shape), B, big
         Q, G, A = problem(shape, B, dtype, prob)
-        self.per_qp, self.side, self.side_rel = [], {}, {}
+        self.per_qp, self.side, self.side_rel = {}, {}, {}          # (per_qp: QP -> its arrays; qps: the QPs that get one)
         floor = TOL_F32 if dtype == "f32" else TOL
-        for i in range(B):
+        for i in (range(B) if qps is None else qps):
             if big:
                 # (the gate of R is not known before its lapack figure is: the two routes to R are first held to 1e-3 x the
                 # floor, and to 1e-3 x the gate of R below)
@@ -279,7 +282,7 @@ class Ref:
                 ref = R.reference(Q[i], G[i], A[i])
                 lap = _side_f32(Q[i], G[i], A[i]) if dtype == "f32" else R.lapack_side(Q[i], G[i], A[i])
                 side = {k: figs(np.asarray(lap[k], np.float64).reshape(1, -1), np.asarray(ref[k], np.float64).reshape(1, -1)) for k in R.NAMES_A}
-            self.per_qp.append(ref)
+            self.per_qp[i] = ref
             for k, v in side.items():
                 self.side[k] = max(v, self.side.get(k, 0.0))
             if not big:
@@ -287,7 +290,7 @@ class Ref:
                     self.side_rel[k] = max(rel(lap[k], ref[k]), self.side_rel.get(k, 0.0))
         self.gate = {k: max(floor, LAPACK_FACTOR * v) for k, v in self.side.items()}
         self.gate_rel = {k: max(floor, LAPACK_FACTOR * v) for k, v in self.side_rel.items()}
-        self.resid = max(r["resid"] for r in self.per_qp)
+        self.resid = max(r["resid"] for r in self.per_qp.values())
         # || dX || <= || X || || I - H X ||: the residual bounds the reference's error relative to the LARGEST block of H^-1, the
         # one that carries the conditioning and has the case's largest gate (K; Lq^-1 in the large family) -- that gate it is
         # held to.  (What np.longdouble leaves of it is its own rounding, 2^-64 |H| |X|: 8.9e-12 at cond(Q) = 1e8, where the
@@ -301,8 +304,9 @@ class Ref:
         return self.side["R" if name in R.IMAGE_INDEX else name]
 
 
-def reference(shape, B, dtype="f64", prob="prof", big=False):
-    return cached(("ref", tuple(shape), B, dtype, prob, big), lambda: Ref(shape, B, dtype, prob, big))
+def reference(shape, B, dtype="f64", prob="prof", big=False, qps=None):
+    key = ("ref", tuple(shape), B, dtype, prob, big) + (() if qps is None else (tuple(qps),))
+    return cached(key, lambda: Ref(shape, B, dtype, prob, big, qps))
 
 
 class Built:
@@ -381,10 +385,11 @@ def expected(ref, i, fam, lay, w=None):
     return exp, np.flatnonzero(kind == 2), kind != 1
 
 
-def compare(g, key, built, ref, fam, lay, ws=None, only=None):
-    """every compared array of every QP of `built` against the reference (worst over the QPs per array), the pads exact zeros"""
+def compare(g, key, built, ref, fam, lay, ws=None, only=None, qps=None):
+    """every compared array of every QP of `built` (of the QPs `qps`) against the reference (worst over the QPs per array), the
+    pads exact zeros"""
     worst, worst_rel = {}, {}
-    for i in range(built.blob.shape[0]):
+    for i in (range(built.blob.shape[0]) if qps is None else qps):
         exp, pads, _ = expected(ref, i, fam, lay, None if ws is None else ws[i])
         for name, (idx, vals) in exp.items():
             if only is None or name in only:
@@ -399,10 +404,11 @@ def compare(g, key, built, ref, fam, lay, ws=None, only=None):
 
 
 # ---------------------------------------------------------------- 1, 2, 3: every word
-def check_blob(env, shape, knob, dtype="f64", prob="prof", check="blob"):
-    B = batch_of(shape, knob)
+def check_blob(env, shape, knob, dtype="f64", prob="prof", check="blob", B=None):
+    key = ("built", env.dev.type, tuple(shape), knob, dtype, prob) + (() if B is None else (B,))
+    B = batch_of(shape, knob, B)
     fam = expected_family(shape, knob, dtype)[0]
-    built = cached(("built", env.dev.type, tuple(shape), knob, dtype, prob), lambda: Built(env, shape, problem(shape, B, dtype, prob), knob, dtype))
+    built = cached(key, lambda: Built(env, shape, problem(shape, B, dtype, prob), knob, dtype))
     assert (built.status == 0).all() and built.blob.shape[0] == B
     fam, lay = layout_of(shape, knob, dtype, built)
     ref = reference(shape, B, dtype, prob, fam == FAMILY_BIG)
