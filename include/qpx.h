@@ -506,6 +506,40 @@ size_t qpx_batch_outer_workspace_elems(int dtype, int B, int r, int c);
  * constraints uses it for the neq x neq correction of the regularised (y, y) block. */
 int qpx_dense_solve(int dtype, int B, int k, void* M, void* rhs, int32_t* status, qpx_stream_t stream);
 
+/* ---- Scenario batches (additive in v8): B groups of K consecutive QPs.  A group shares (Q, G, A) and so ONE
+ * factor blob -- `factors` holds B blobs, written by qpx_pre_factor(dtype, B, ...) -- while every per-QP array (p, h, b with
+ * a non-zero stride, the outputs, iters, status, best_resid, trace) has B K rows: QP j = g K + k reads blob g.  `status` has
+ * B K words too: the caller repeats the pre-factorisation's word of group g for its K QPs.
+ *
+ * qpx_group_supported: 1 exactly where qpx_can_share_factors is 1 (the kernels only read the blob) and a loop form and a
+ * backward form serve the size under the calling thread's knob; 0 for the large-QP family. */
+int qpx_group_supported(int dtype, int n, int m, int q);
+/* qpx_ipm on the B K QPs (its arguments, its results bit for bit: the form is picked for B K QPs by qpx_ipm's rule and the
+ * per-QP arithmetic is the same; only the blob's address differs).  sfac: the stride between GROUPS' blobs.  K < 1 or a NULL
+ * that qpx_ipm refuses: QPX_ERR_ARG; a size without qpx_group_supported: QPX_ERR_UNSUPPORTED, before any launch. */
+int qpx_ipm_group(int dtype, int B, int K, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
+                  const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
+                  int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
+                  void* best_resid, void* trace, qpx_stream_t stream);
+/* qpx_backward_duals on the B K QPs: dp, dh, db are written per QP (B K rows, any may be NULL).  dQ, dG, dA must be NULL
+ * (QPX_ERR_ARG otherwise): a group's matrix gradient is the SUM over its K QPs -- ask for dx, dz, dy (B K rows) and contract
+ * them with qpx_group_outer.  refine must be 0 (Q, G, A are ignored); refine > 0 or an unsupported size:
+ * QPX_ERR_UNSUPPORTED, before any launch. */
+int qpx_backward_group(int dtype, int B, int K, int n, int m, int q, void* factors, int64_t sfac, const void* zhat,
+                       const void* lam, const void* slack, const void* nu, const void* dl_dz, const void* dl_dlam,
+                       const void* dl_dnu, void* dQ, void* dp, void* dG, void* dh, void* dA, void* db, void* dx, void* dz,
+                       void* dy, int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
+                       int32_t* status, qpx_stream_t stream);
+/* The grouped mode of qpx_batch_outer: out (B,r,c),
+ *   out[g] = scale * sum_{k < K} ( u[j][r] v[j][c] + w[j][r] x[j][c] ),  j = g K + k        u, w: (B K,r)  v, x: (B K,c)
+ * (scale is NOT divided by anything; v, w, x NULL as for qpx_batch_outer).  dQ: u = dx, v = zhat, w = zhat, x = dx,
+ * scale = 0.5; dG: u = dz, v = zhat, w = lam, x = dx; dA: u = dy, v = zhat, w = nu, x = dx.  Fixed order of additions, no
+ * atomics: bit-reproducible.  B > 1 needs `ws`, at least qpx_group_outer_workspace_elems elements of dtype (QPX_ERR_ARG
+ * otherwise); QPX_F32 / QPX_F64 only (a QPX_F32_WIDE caller passes QPX_F32, as for qpx_batch_outer). */
+int qpx_group_outer(int dtype, int B, int K, int r, int c, const void* u, const void* v, const void* w, const void* x,
+                    double scale, void* out, void* ws, size_t ws_elems, qpx_stream_t stream);
+size_t qpx_group_outer_workspace_elems(int dtype, int B, int K, int r, int c);
+
 #ifdef __cplusplus
 }
 #endif

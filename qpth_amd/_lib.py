@@ -86,6 +86,13 @@ _SIGNATURES = {
     "qpx_batch_outer": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, ctypes.c_size_t, _vp]),
     "qpx_batch_outer_workspace_elems": (ctypes.c_size_t, [_i, _i, _i, _i]),
     "qpx_dense_solve": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    "qpx_group_supported": (_i, [_i, _i, _i, _i]),
+    "qpx_ipm_group": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _d, _i, _i, _i,
+                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qpx_backward_group": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "qpx_group_outer": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, ctypes.c_size_t, _vp]),
+    "qpx_group_outer_workspace_elems": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
 }
 ABI_SYMBOLS = tuple(_SIGNATURES)
 
@@ -354,6 +361,39 @@ class QpxLib:
         self.check(self.dll.qpx_batch_outer(code, B, r, c, _ptr(u), _ptr(v), _ptr(w), _ptr(x),
                                             float(scale), _ptr(out), _ptr(ws), need, _stream(out)))
 
+
+    # -- scenario batches: B groups of K consecutive QPs, one blob per group ----------------------
+    def group_supported(self, dtype_code, n, m, q):
+        return bool(self.dll.qpx_group_supported(dtype_code, n, m, q))
+
+    def ipm_group(self, B, K, n, m, q, p, h, b, factors, sfac, eps, maxIter, notImprovedLim, stall_policy,
+                  zhat, nu, lam, slack, iters, status, best_resid, trace=None, wide=False):
+        """qpx_ipm_group: every per-QP tensor has B K rows (p, h, b may be shared: batch stride 0); `factors` holds B blobs"""
+        pp, hp, bp = Param(p, 2), Param(h, 2), Param(b, 2)
+        self.check(self.dll.qpx_ipm_group(
+            _code(factors, wide), B, int(K), n, m, q, pp.ptr, pp.stride, hp.ptr, hp.stride, bp.ptr, bp.stride,
+            _ptr(factors), int(sfac), float(eps), int(maxIter), int(notImprovedLim), int(stall_policy),
+            _ptr(zhat), _ptr(nu), _ptr(lam), _ptr(slack), _ptr(iters), _ptr(status), _ptr(best_resid),
+            _ptr(trace), _stream(factors)))
+
+    def backward_group(self, B, K, n, m, q, factors, sfac, zhat, lam, slack, nu, dl_dz, dp, dh, db, status,
+                       dx=None, dz=None, dy=None, wide=False, dl_dlam=None, dl_dnu=None):
+        """qpx_backward_group: dp, dh, db per QP (any may be None); the matrices' gradients come from dx, dz, dy (group_outer)"""
+        self.check(self.dll.qpx_backward_group(
+            _code(factors, wide), B, int(K), n, m, q, _ptr(factors), int(sfac), _ptr(zhat), _ptr(lam), _ptr(slack),
+            _ptr(nu), _ptr(dl_dz), _ptr(dl_dlam), _ptr(dl_dnu), None, _ptr(dp), None, _ptr(dh), None, _ptr(db),
+            _ptr(dx), _ptr(dz), _ptr(dy), 0, None, 0, None, 0, None, 0, _ptr(status), _stream(factors)))
+
+    def group_outer(self, K, u, v, w, x, scale, out):
+        """out (B, r, c): out[g] = scale * sum over group g's K consecutive rows of (u^T v + w^T x); w, x None: one product"""
+        BK, r = u.shape
+        B, c = BK // int(K), v.shape[1]
+        assert B * int(K) == BK and out.shape == (B, r, c) and out.is_contiguous()
+        code = _dtype_code(out)
+        need = int(self.dll.qpx_group_outer_workspace_elems(code, B, int(K), r, c))
+        ws = torch.empty(need, dtype=out.dtype, device=out.device) if need else None
+        self.check(self.dll.qpx_group_outer(code, B, int(K), r, c, _ptr(u), _ptr(v), _ptr(w), _ptr(x),
+                                            float(scale), _ptr(out), _ptr(ws), need, _stream(out)))
 
     # -- the neq x neq correction of factor_solve_kkt_reg (batch.py:273-310): x = M^-1 r, M destroyed, r overwritten
     def dense_solve(self, M, rhs, status=None):

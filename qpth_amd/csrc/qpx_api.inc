@@ -178,10 +178,13 @@ int api_ipm(int B, int n, int m, int q, const void* p, int64_t sp, const void* h
             const void* bb, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
             int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters,
             int32_t* status, void* best_resid, void* trace, void* stream, int io32 = 0,
-            const void* lam0 = nullptr, const void* s0 = nullptr, double warm_floor = 0, int32_t* warm_used = nullptr)
+            const void* lam0 = nullptr, const void* s0 = nullptr, double warm_floor = 0, int32_t* warm_used = nullptr,
+            int fac_group = 0, bool launch = true)
 {
-    if (!p || !h || !factors || !zhat || !lam || !slack || !iters || !status || !best_resid ||
-        (q > 0 && (!nu || !bb)))
+    // (launch = false: the decision only -- QPX_OK where a form serves B QPs of this size under the calling thread's knob;
+    // fac_group: IpmArgs::fac_group, scenario batches -- qpx_ipm_group)
+    if (launch && (!p || !h || !factors || !zhat || !lam || !slack || !iters || !status || !best_resid ||
+        (q > 0 && (!nu || !bb))))
         return QPX_ERR_ARG;
     if (maxIter < 0 || stall_policy < 0 || stall_policy > 2) return QPX_ERR_ARG;
     if ((lam0 == nullptr) != (s0 == nullptr)) return QPX_ERR_ARG;
@@ -190,8 +193,10 @@ int api_ipm(int B, int n, int m, int q, const void* p, int64_t sp, const void* h
     ipm_common_args(a, B, n, m, q, p, sp, h, sh, bb, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters, status,
                     best_resid, trace);
     a.lam0 = (const T*)lam0; a.s0 = (const T*)s0; a.warm_floor = (T)warm_floor; a.warm_used = lam0 ? warm_used : nullptr;
+    a.fac_group = fac_group;
     a.images = blob_images<T>(n, m, q);
     if (a.images == 8) {
+        if (fac_group > 1 || !launch) return QPX_ERR_UNSUPPORTED;      // per-QP work matrices live in the blob: no groups (qpx_group_supported)
         if (lam0) return QPX_ERR_UNSUPPORTED;             // the large-QP family's start point is a launch sequence of its own: no warm entry (qpx_warm_supported)
         if (sfac == 0 && B > 1) return QPX_ERR_ARG;       // per-QP work matrices live in the blob
         return big_split(B, stream, a.trace == nullptr, [&](int q0, int cnt, void* st, int part, int nparts) {     // trace is indexed [it][B][3]
@@ -218,7 +223,7 @@ int api_ipm(int B, int n, int m, int q, const void* p, int64_t sp, const void* h
         if (((g_grid_size == 0 && chip_full && !(std::is_same<T, double>::value && tile_nb(m) > 0)) || g_grid_size == 8) && nb8 > 0 && (ns8 == 1 || ns8 == 2) &&
             !(ns8 == 1 && nb8 > 8)) {
             const size_t wb = lds_elems_ipm_grid(8, nb8, n, q) * sizeof(T);
-#define QPX_PICK(NBL, NS) if (nb8 == NBL && ns8 == NS) return launch_ipm_grid8<T, NBL, NS>(a, wb, stream);
+#define QPX_PICK(NBL, NS) if (nb8 == NBL && ns8 == NS) return launch ? launch_ipm_grid8<T, NBL, NS>(a, wb, stream) : QPX_OK;
             QPX_FORMS_IPM_GRID8(QPX_PICK)           // no such form: on to the tiles / the 16x16 grid
 #undef QPX_PICK
         }
@@ -237,7 +242,7 @@ int api_ipm(int B, int n, int m, int q, const void* p, int64_t sp, const void* h
                 // occupancy is read off without rebuilding it)
                 static const size_t lds_pad = [] { const char* e = std::getenv("QPX_LDS_PAD_BYTES"); return e ? (size_t)std::atol(e) : (size_t)0; }();
                 const size_t tb = lds_elems_ipm_tile(nbt, nw, n, q, ch) * sizeof(T) + lds_pad;
-#define QPX_PICK(NBL, NW, NS, CH) if (nbt == NBL && nw == NW && nst == NS && ch == CH) return launch_ipm_tile<NBL, NW, NS, CH>(a, tb, stream);
+#define QPX_PICK(NBL, NW, NS, CH) if (nbt == NBL && nw == NW && nst == NS && ch == CH) return launch ? launch_ipm_tile<NBL, NW, NS, CH>(a, tb, stream) : QPX_OK;
                 QPX_FORMS_IPM_TILE(QPX_PICK)        // no such form: on to the 16x16 grid
 #undef QPX_PICK
             }
@@ -245,7 +250,7 @@ int api_ipm(int B, int n, int m, int q, const void* p, int64_t sp, const void* h
         const int nbg = grid_nb(m);
         const int nsg = slots_for(n, 16 * nbg, q);
         const size_t gb = lds_elems_ipm_grid(16, nbg, n, q) * sizeof(T);
-#define QPX_PICK(NBL, NS) if (nbg == NBL && nsg == NS) return launch_ipm_grid<T, NBL, NS>(a, gb, stream);
+#define QPX_PICK(NBL, NS) if (nbg == NBL && nsg == NS) return launch ? launch_ipm_grid<T, NBL, NS>(a, gb, stream) : QPX_OK;
         QPX_FORMS_IPM_GRID(QPX_PICK)
 #undef QPX_PICK
         return QPX_ERR_UNSUPPORTED;
@@ -255,8 +260,9 @@ int api_ipm(int B, int n, int m, int q, const void* p, int64_t sp, const void* h
 
 // kRole: 0 the KKT solve, 1 the backward, 2 the solve for a.K right-hand sides per QP (qpx_forms.h: kKktMultiRole) -- the
 // third role of the form the first two run in, so all three follow one rule for which form serves a size
+// (launch = false: the decision only -- QPX_OK where a form serves a.B QPs of this size under the calling thread's knob)
 template <class T, int kRole>
-int api_kkt(KktArgs<T>& a, void* stream)
+int api_kkt(KktArgs<T>& a, void* stream, bool launch = true)
 {
     constexpr bool kBw = kRole == 1;
     constexpr int kForm = kRole == 2 ? kKktMultiRole : 0;
@@ -265,6 +271,7 @@ int api_kkt(KktArgs<T>& a, void* stream)
     if constexpr (kRole == 2) {
         if (a.images == 8) return QPX_ERR_UNSUPPORTED;       // the large-QP family has no such kernels: K calls of the single solve
     } else if (a.images == 8) {
+        if (a.fac_group > 1 || !launch) return QPX_ERR_UNSUPPORTED;      // (as api_ipm: no groups in the large-QP family)
         if (a.fac_stride == 0 && a.B > 1) return QPX_ERR_ARG;
         // (parts only when the knob asks for them: one factorisation + one solve is too short a sequence for two parts to
         // fill each other's gaps -- same box, backward by events, one part / two: C4 0.643 / 0.645 ms, B=128 n=300 m=200 q=50
@@ -294,14 +301,14 @@ int api_kkt(KktArgs<T>& a, void* stream)
                 const int nw = tile_waves(nbt, a.B);
                 const bool ch = tile_chain(nbt, nw);
                 const size_t tb = (kRole == 2 ? lds_elems_kkt_multi_tile(nbt, nw, n, q, ch) : lds_elems_kkt_tile(nbt, nw, n, q, ch)) * sizeof(T);
-#define QPX_PICK(NBL, NW, CH) if (nbt == NBL && nw == NW && ch == CH) return launch_kkt_tile<kForm + NBL, NW, kBw, CH>(a, tb, stream);
+#define QPX_PICK(NBL, NW, CH) if (nbt == NBL && nw == NW && ch == CH) return launch ? launch_kkt_tile<kForm + NBL, NW, kBw, CH>(a, tb, stream) : QPX_OK;
                 QPX_FORMS_KKT_TILE(QPX_PICK)        // no such form: on to the 16x16 grid
 #undef QPX_PICK
             }
         }
         const int nbg = grid_nb(m);
         const size_t gb = (kRole == 2 ? lds_elems_kkt_multi_grid(16, nbg, n, q) : lds_elems_kkt_grid(16, nbg, n, q)) * sizeof(T);
-#define QPX_PICK(NBL) if (nbg == NBL) return launch_kkt_grid<T, kForm + NBL, kBw>(a, gb, stream);
+#define QPX_PICK(NBL) if (nbg == NBL) return launch ? launch_kkt_grid<T, kForm + NBL, kBw>(a, gb, stream) : QPX_OK;
         QPX_FORMS_KKT_GRID(QPX_PICK)
 #undef QPX_PICK
         return QPX_ERR_UNSUPPORTED;
@@ -348,11 +355,12 @@ template <class T>
 int api_backward(int io32, int B, int n, int m, int q, void* factors, int64_t sfac, const void* zhat, const void* lam,
                  const void* slack, const void* nu, const void* dl_dz, const void* dl_dlam, const void* dl_dnu, void* dQ, void* dp,
                  void* dG, void* dh, void* dA, void* db, void* dx, void* dz, void* dy, int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A,
-                 int64_t sA, int32_t* status, void* stream)
+                 int64_t sA, int32_t* status, void* stream, int fac_group = 0)
 {
     KktArgs<T> a{};
     a.io32 = io32;
     a.B = B; a.n = n; a.m = m; a.q = q; a.fac = (T*)factors; a.fac_stride = (size_t)sfac;
+    a.fac_group = fac_group;              // scenario batches (qpx_backward_group); else 0
     a.zhat = (const T*)zhat; a.lam = (const T*)lam; a.slack = (const T*)slack; a.nu = (const T*)nu; a.dl_dz = (const T*)dl_dz;
     a.dl_dlam = (const T*)dl_dlam; a.dl_dnu = q > 0 ? (const T*)dl_dnu : nullptr;
     a.dQ = (T*)dQ; a.dp = (T*)dp; a.dG = (T*)dG; a.dh = (T*)dh; a.dA = (T*)dA; a.db = (T*)db; a.status = status;
@@ -632,6 +640,50 @@ int api_batch_outer(int B, int r, int c, const void* u, const void* v, const voi
     a.chunk_len = outer_chunk_len(B, a.chunks);
     a.ws = a.chunks > 1 ? (T*)ws : nullptr;
     return launch_batch_outer<T>(a, tiles, stream);
+}
+
+// Scenario batches (DESIGN 4.15): K consecutive QPs per factorisation.  Served where the blob is only read -- the thread-grid /
+// tile families, qpx_can_share_factors -- and a loop form and a backward form exist for the size under the calling thread's
+// knob (every default choice does; a small and a large batch cover both choices of the rules that depend on B).
+template <class T> inline bool group_served_t(int n, int m, int q, int io32)
+{
+    for (const int B : {1, 1 << 20}) {
+        if (api_ipm<T>(B, n, m, q, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0.0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, io32, nullptr, nullptr, 0, nullptr, 0, false) != QPX_OK)
+            return false;
+        KktArgs<T> ka{};
+        ka.B = B; ka.n = n; ka.m = m; ka.q = q; ka.io32 = io32;
+        if (api_kkt<T, 1>(ka, nullptr, false) != QPX_OK) return false;
+    }
+    return true;
+}
+inline bool group_served(int dtype, int n, int m, int q)
+{
+    if (check_dims(dtype, 1, n, m, q) != QPX_OK || use_big(n, m, q, dtype != QPX_F32 ? 8 : 4)) return false;
+    return dtype != QPX_F32 ? group_served_t<double>(n, m, q, dtype == QPX_F32_WIDE) : group_served_t<float>(n, m, q, 0);
+}
+
+// out (B, r, c), out[g] = scale ( U_g^T V_g + W_g^T X_g ) over group g's K consecutive rows: the grouped mode of the batch
+// contraction (qpx_reduce.h), a slab of groups per pair of launches
+template <class T>
+int api_group_outer(int B, int K, int r, int c, const void* u, const void* v, const void* w, const void* x, double scale,
+                    void* out, void* ws, size_t ws_elems, void* stream)
+{
+    const int tiles = ((r + 15) / 16) * ((c + 15) / 16), slab = group_slab(B, tiles);
+    if (slab > 1 && (!ws || ws_elems < (size_t)slab * tiles * 256)) return QPX_ERR_ARG;
+    for (int g0 = 0; g0 < B; g0 += slab) {
+        const int cnt = B - g0 < slab ? B - g0 : slab;
+        const size_t row0 = (size_t)g0 * K;
+        OuterArgs<T> a;
+        a.B = cnt * K; a.r = r; a.c = c;
+        a.u = (const T*)u + row0 * r; a.v = v ? (const T*)v + row0 * c : nullptr;
+        a.w = w ? (const T*)w + row0 * r : nullptr; a.x = w ? (const T*)x + row0 * c : nullptr;
+        a.scale = (T)scale; a.out = (T*)out + (size_t)g0 * r * c;
+        a.grouped = 1; a.chunks = cnt; a.chunk_len = K;
+        a.ws = cnt > 1 ? (T*)ws : nullptr;
+        if (const int e = launch_batch_outer<T>(a, tiles, stream)) return e;
+    }
+    return QPX_OK;
 }
 
 }  // namespace qpx
@@ -1122,6 +1174,66 @@ int qpx_batch_outer(int dtype, int B, int r, int c, const void* u, const void* v
     if ((!v && c != 1) || (!w) != (!x)) return QPX_ERR_ARG;       // v8: v == NULL = a column of ones; w, x both or neither
     return dtype == QPX_F64 ? qpx::api_batch_outer<double>(B, r, c, u, v, w, x, scale, out, ws, ws_elems, stream)
                             : qpx::api_batch_outer<float>(B, r, c, u, v, w, x, scale, out, ws, ws_elems, stream);
+}
+
+/* ---- scenario batches (DESIGN 4.15): B groups of K consecutive QPs, one factor blob per group ---- */
+
+int qpx_group_supported(int dtype, int n, int m, int q) { return qpx::group_served(dtype, n, m, q) ? 1 : 0; }
+
+int qpx_ipm_group(int dtype, int B, int K, int n, int m, int q, const void* p, int64_t sp, const void* h, int64_t sh,
+                  const void* b, int64_t sb, void* factors, int64_t sfac, double eps, int maxIter, int notImprovedLim,
+                  int stall_policy, void* zhat, void* nu, void* lam, void* slack, int32_t* iters, int32_t* status,
+                  void* best_resid, void* trace, qpx_stream_t stream)
+{
+    if (K < 1 || B < 1 || (int64_t)B * K > 0x7fffffff) return QPX_ERR_ARG;
+    const int e = qpx::check_dims(dtype, B * K, n, m, q);
+    if (e) return e;
+    if (!p || !h || !factors || !zhat || !lam || !slack || !iters || !status || !best_resid || (q > 0 && (!nu || !b))) return QPX_ERR_ARG;
+    if (!qpx::group_served(dtype, n, m, q)) return QPX_ERR_UNSUPPORTED;
+    return dtype != QPX_F32
+               ? qpx::api_ipm<double>(B * K, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters, status, best_resid, trace, stream, dtype == QPX_F32_WIDE,
+                                      nullptr, nullptr, 0, nullptr, K)
+               : qpx::api_ipm<float>(B * K, n, m, q, p, sp, h, sh, b, sb, factors, sfac, eps, maxIter, notImprovedLim, stall_policy, zhat, nu, lam, slack, iters, status, best_resid, trace, stream, 0,
+                                     nullptr, nullptr, 1e-2, nullptr, K);
+}
+
+int qpx_backward_group(int dtype, int B, int K, int n, int m, int q, void* factors, int64_t sfac, const void* zhat,
+                       const void* lam, const void* slack, const void* nu, const void* dl_dz, const void* dl_dlam,
+                       const void* dl_dnu, void* dQ, void* dp, void* dG, void* dh, void* dA, void* db, void* dx, void* dz,
+                       void* dy, int refine, const void* Q, int64_t sQ, const void* G, int64_t sG, const void* A, int64_t sA,
+                       int32_t* status, qpx_stream_t stream)
+{
+    if (K < 1 || B < 1 || (int64_t)B * K > 0x7fffffff) return QPX_ERR_ARG;
+    const int e = qpx::check_dims(dtype, B * K, n, m, q);
+    if (e) return e;
+    if (!factors || !zhat || !lam || !slack || (q > 0 && !nu)) return QPX_ERR_ARG;
+    if (!dl_dz && !dl_dlam && !(q > 0 && dl_dnu)) return QPX_ERR_ARG;       // no cotangent at all
+    if (dQ || dG || dA) return QPX_ERR_ARG;       // a group's matrix gradients are sums over its K QPs: dx, dz, dy and qpx_group_outer
+    if (refine < 0) return QPX_ERR_ARG;
+    if (refine > 0 || !qpx::group_served(dtype, n, m, q)) return QPX_ERR_UNSUPPORTED;
+    (void)Q; (void)sQ; (void)G; (void)sG; (void)A; (void)sA;      // (refinement's data: refine is 0)
+    if (dtype != QPX_F32)
+        return qpx::api_backward<double>(dtype == QPX_F32_WIDE, B * K, n, m, q, factors, sfac, zhat, lam, slack, nu, dl_dz, dl_dlam, dl_dnu,
+                                         nullptr, dp, nullptr, dh, nullptr, db, dx, dz, dy, 0, nullptr, 0, nullptr, 0, nullptr, 0, status, stream, K);
+    return qpx::api_backward<float>(0, B * K, n, m, q, factors, sfac, zhat, lam, slack, nu, dl_dz, dl_dlam, dl_dnu, nullptr, dp, nullptr, dh,
+                                    nullptr, db, dx, dz, dy, 0, nullptr, 0, nullptr, 0, nullptr, 0, status, stream, K);
+}
+
+size_t qpx_group_outer_workspace_elems(int dtype, int B, int K, int r, int c)
+{
+    if ((dtype != QPX_F32 && dtype != QPX_F64) || B < 1 || K < 1 || r < 1 || c < 1) return 0;
+    const int tiles = ((r + 15) / 16) * ((c + 15) / 16), slab = qpx::group_slab(B, tiles);
+    return slab > 1 ? (size_t)slab * tiles * 256 : 0;
+}
+
+int qpx_group_outer(int dtype, int B, int K, int r, int c, const void* u, const void* v, const void* w, const void* x,
+                    double scale, void* out, void* ws, size_t ws_elems, qpx_stream_t stream)
+{
+    if (dtype != QPX_F32 && dtype != QPX_F64) return QPX_ERR_ARG;
+    if (B < 1 || K < 1 || (int64_t)B * K > 0x7fffffff || r < 1 || c < 1 || !u || !out) return QPX_ERR_ARG;
+    if ((!v && c != 1) || (!w) != (!x)) return QPX_ERR_ARG;       // as qpx_batch_outer
+    return dtype == QPX_F64 ? qpx::api_group_outer<double>(B, K, r, c, u, v, w, x, scale, out, ws, ws_elems, stream)
+                            : qpx::api_group_outer<float>(B, K, r, c, u, v, w, x, scale, out, ws, ws_elems, stream);
 }
 
 }  // extern "C"

@@ -1736,7 +1736,9 @@ QPX_DEV void ipm_loop_role(const Block& b, const IpmArgs<T>& a, int qp, T* lds, 
     constexpr int M8 = Mat::MP, NT = Mat::NT;
     const int n = a.n, m = a.m, q = a.q;
     const FacLayout lay = fac_layout(n, m, q, a.images);
-    T* F = a.fac + (size_t)qp * a.fac_stride;
+    // (scenario batches, DESIGN 4.15: the hard loop's forms -- the ones qpx_ipm_group launches -- map the QP to its group's blob;
+    // the row roles' entry points have no groups, and their forms compile the parent's address)
+    T* F = a.fac + (size_t)(kRole == 0 ? fac_index(qp, a.fac_group) : qp) * a.fac_stride;
     const T* Rg = Mat::image(F, lay);
     // compile-time vector stride (64 NS >= max(n, MP, q)): every LDS vector is then a constant offset
     // from one base and the compiler addresses them all with one lane register + immediates (with a
@@ -2703,7 +2705,8 @@ QPX_DEV void kkt_mat_role(const Block& b, const KktArgs<T>& a, int qp, T* lds, c
     constexpr int M8 = Mat::MP, NT = Mat::NT;
     const int n = a.n, m = a.m, q = a.q;
     const FacLayout lay = fac_layout(n, m, q, a.images);
-    T* F = a.fac + (size_t)qp * a.fac_stride;
+    // (scenario batches: the backward's own instantiation -- what qpx_backward_group launches -- maps the QP to its group's blob)
+    T* F = a.fac + (size_t)(kBackward && !kRange ? fac_index(qp, a.fac_group) : qp) * a.fac_stride;
     const size_t v = align4(max2(max2((size_t)n, (size_t)M8), (size_t)q));
     T* rd = lds;
     T* vD = rd + v;       // 1/d, 1 on the pad

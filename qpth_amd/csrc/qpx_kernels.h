@@ -131,6 +131,11 @@ template <class T> QPX_DEV bool soft_blob(const Block& b, const In<T>& wg, int m
 }
 
 // ------------------------------------------------------------------------------------------
+// Which blob QP `qp` reads (IpmArgs / KktArgs::fac_group): its own, or -- scenario batches, DESIGN 4.15 -- the one its group of
+// `group` consecutive QPs shares.  qp is the workgroup's index and group a kernel argument: a uniform division, once per launch
+QPX_LAYOUT_HD int fac_index(int qp, int group) { return group > 1 ? (int)((unsigned)qp / (unsigned)group) : qp; }
+
+// ------------------------------------------------------------------------------------------
 // kernel argument blocks (plain data, passed by value)
 
 template <class T> struct PrefactorArgs {
@@ -193,6 +198,9 @@ template <class T> struct IpmArgs {
     // QP is warm if lam0, s0 are finite on every row and lam0_lo, s0_lo on every row that is two-sided in THIS call (the
     // entries of a one-sided row are never read: a previous solve left 0 and +inf there); any other QP starts cold
     const T *lam0_lo = nullptr, *s0_lo = nullptr;
+    // scenario batches (qpx_ipm_group): QP `qp` reads blob qp / fac_group -- fac_group consecutive QPs share one
+    // factorisation; 0 or 1 = one blob per QP (or, with fac_stride 0, one for the batch).  Everything else stays per QP
+    int fac_group = 0;
 };
 
 template <class T> struct KktArgs {
@@ -228,6 +236,8 @@ template <class T> struct KktArgs {
     // the backward of two-sided rows (qpx_backward_range; the forms of kKktRangeRole only): the lower side's multipliers and
     // slacks (B,m) -- d = clamp(lam)/clamp(slack) + clamp(lam_lo)/clamp(slack_lo), lam - lam_lo in the outer products
     const T *lam_lo = nullptr, *slack_lo = nullptr;
+    // scenario batches (qpx_backward_group): blob index = qp / fac_group, as IpmArgs::fac_group (kkt_mat_role only)
+    int fac_group = 0;
 };
 
 // The finishing stage (qpx_polish, include/qpx.h): iterations of the reference's loop in the ORIGINAL variables

@@ -18,6 +18,10 @@
 // reference's `.mean(0)` is (no atomics).  Operand loads are unconditional (a lane outside the arrays re-reads the last
 // row / column and its value is deselected afterwards): a load whose only use sits under a lane condition is sunk into
 // the condition and costs a round trip to memory per element.
+// GROUPED MODE (scenario batches): the batch is B groups of K consecutive QPs and every group keeps its own sum,
+// out[g] = scale ( U_g^T V_g + W_g^T X_g ) -- the gradient of a matrix that K scenarios share.  The same two launches:
+// chunk = group (chunk_len = K, any K: the clamped loads deselect the rows beyond a group's last, a neighbour's among
+// them), and the second stage adds nothing -- it writes each group's partial tile, scaled, to out + g r c.
 #pragma once
 #include "qpx_kernels.h"
 
@@ -30,11 +34,22 @@ template <class T> struct OuterArgs {
     T* out;
     T* ws;            // two-stage form: chunks x tiles x 256 partial sums (accumulator layout); else null
     int chunks;       // parts of the batch (1: `out` is written directly)
-    int chunk_len;    // QPs per chunk (a multiple of 16 x kOuterWaves)
+    int chunk_len;    // QPs per chunk (a multiple of 16 x kOuterWaves; grouped mode: K)
+    int grouped = 0;  // 1: chunk = group, `out` is (chunks, r, c) and `scale` is not divided by anything (see above)
 };
 constexpr int kOuterWaves = 16;      // waves per workgroup = parts of a chunk
 constexpr int kOuterTrip = 16 * kOuterWaves;      // QPs one trip of a workgroup covers
 constexpr int kOuterMaxChunks = 64;
+// grouped mode: groups one pair of launches takes -- the workspace holds a partial tile per (group, tile), at most
+// kGroupWsElems elements (128 MB in f64), and the groups are the grid's second dimension (<= 65 535)
+constexpr size_t kGroupWsElems = (size_t)1 << 24;
+QPX_LAYOUT_HD int group_slab(int groups, int tiles)
+{
+    size_t s = kGroupWsElems / ((size_t)tiles * 256);
+    if (s > 65535) s = 65535;
+    if (s < 1) s = 1;
+    return (size_t)groups < s ? groups : (int)s;
+}
 
 // How a batch is cut (host and tests): chunks of whole trips, enough (tile, chunk) workgroups to fill the chip a few
 // times over, never more than kOuterMaxChunks; one chunk = the single-stage form.
@@ -114,9 +129,20 @@ template <class T> QPX_DEV void batch_outer_sum_body(const Block& b, const Outer
     const int tc = (a.c + 15) >> 4, ntiles = tc * ((a.r + 15) >> 4);
     const int I = tile / tc, J = tile - I * tc;
     const int e = b.tid, rr = e >> 6, lane = e & 63, g = lane >> 4, c16 = lane & 15;
+    const int i = 16 * I + Block::mfma_row(T(0), g, rr), j = 16 * J + c16;
+    if (a.grouped) {
+        // a tile per group: nothing to add (the iterations are independent: sixteen loads in flight per lane)
+        const bool ok = i < a.r && j < a.c;
+        const size_t o = ok ? (size_t)i * a.c + j : 0, rc = (size_t)a.r * a.c;
+#pragma unroll 16
+        for (int k = 0; k < a.chunks; ++k) {
+            const T part = a.ws[((size_t)k * ntiles + tile) * 256 + e];
+            if (ok) a.out[(size_t)k * rc + o] = a.scale * part;
+        }
+        return;
+    }
     T sum = T(0);
     for (int k = 0; k < a.chunks; ++k) sum += a.ws[((size_t)k * ntiles + tile) * 256 + e];
-    const int i = 16 * I + Block::mfma_row(T(0), g, rr), j = 16 * J + c16;
     if (i < a.r && j < a.c) a.out[(size_t)i * a.c + j] = a.scale * sum;
 }
 

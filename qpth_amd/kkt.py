@@ -284,8 +284,15 @@ class KKTFactors:
     _entry_words = None      # (status and bad-entry words, event, messages) of a row role's launch, until raise_on_failure reads them
 
     @classmethod
-    def build(cls, Q, G, A, nBatch=None, wide=False, w=None):
+    def build(cls, Q, G, A, nBatch=None, wide=False, w=None, scenarios=None):
         """pre_factor_kkt(Q, G, A)   (batch.py:375-429); enqueues one kernel, no host sync.
+        scenarios=K: nBatch GROUPS of K consecutive QPs, a group sharing its (Q, G, A) and so one blob -- nBatch
+        blobs are built, and everything behind build() works on nBatch K QPs: `B` is nBatch K, `status` has nBatch K words
+        (a group's pre-factorisation word repeated for its K QPs), ipm / backward (duals' cotangents included) /
+        raise_on_failure take and return nBatch K rows; backward hands a batched matrix's gradient back per GROUP, (nBatch, ., .),
+        summed over the group's QPs.  Sizes of qpx_group_supported only (RuntimeError otherwise), no soft rows; the launches
+        beside ipm and backward (solve_kkt, polish, centre, jvp, backward2, the row roles) are not served on such factors.
+        Q, G, A all shared by the batch: the one-blob path on nBatch K QPs, as without scenarios.
         wide: float32 tensors, float64 factors and arithmetic (QPX_F32_WIDE, include/qpx.h): every later call on these
         factors takes and returns float32 tensors, the blob is float64.
         w (B, nineq), (1, nineq) or (nineq,), >= 0: soft rows -- the factors of the QP with the penalty 1/2 sum t_i^2 / w_i on
@@ -298,6 +305,18 @@ class KKTFactors:
         if self.wide and Q.dtype != torch.float32:
             raise TypeError("qpth_amd: wide=True is for float32 tensors")
         B = nBatch if nBatch is not None else _batch_of(Q, G, A)
+        self.K = None                 # scenarios per group, or None: one blob per QP / one for the batch
+        if scenarios is not None:
+            K = int(scenarios)
+            if K < 1:
+                raise ValueError("qpth_amd: scenarios must be a positive integer, got %r" % (scenarios,))
+            if self.soft:
+                raise ValueError("qpth_amd: scenarios= with soft rows (w / rho) is not served; build the expanded batch instead")
+            if _is_shared(Q, B) and _is_shared(G, B) and _is_shared(A, B):
+                B = B * K             # nothing is per group: the one-blob path on all the QPs
+            else:
+                self.K = K
+        self.groups = B               # blobs when K is set
         self.B = B
         self.n = Q.size(-1)
         self.m = G.size(-2)
@@ -339,6 +358,13 @@ class KKTFactors:
                           and bool(self.lib.dll.qpx_polish_supported(pcode, self.n, self.m, self.q)))
         share_ok = bool(self.lib.dll.qpx_can_share_factors(code, self.n, self.m, self.q))
         self.shared = B > 1 and share_ok and _is_shared(Q, B) and _is_shared(G, B) and _is_shared(A, B)
+        if self.K is not None:
+            if not self.lib.group_supported(code, self.n, self.m, self.q):
+                raise RuntimeError("qpth_amd: scenarios= is not served at nz = %d, nineq = %d, neq = %d (qpx_group_supported: the "
+                                   "large-QP family keeps per-QP work matrices in the blob); build the expanded batch instead"
+                                   % (self.n, self.m, self.q))
+            self.refine_ok = self.polish_ok = False
+            self.B = B * self.K
         if self.soft:
             self.refine_ok = self.polish_ok = False
             w_shared = w.dim() == 1 or w.stride(0) == 0 or (B > 1 and w.size(0) == 1)
@@ -355,6 +381,12 @@ class KKTFactors:
                                 wide=self.wide, w=w)
         if self.shared:
             self.status[1:] = self.status[0]
+        if self.K is not None:
+            # a word per QP for the loop and the backward to OR their bits into: the group's, K times (the pinned copy below
+            # reads `pre`, the groups' words as the kernel wrote them)
+            pre = self.status
+            # (repeat always materialises -- the kernels index raw words --, one copy kernel, no host sync: capturable)
+            self.status = pre.unsqueeze(1).repeat(1, self.K).reshape(-1)
         # The reference raises on a bad Q / A from inside forward (qp.py:81-85, batch.py:379-386).  The two
         # status bits that matter are final once the pre-factorisation kernel has run, so the status words are
         # copied to pinned host memory right behind it and read (raise_on_failure) after the loop kernel
@@ -367,7 +399,7 @@ class KKTFactors:
             if not torch.cuda.is_current_stream_capturing():
                 self._pre_key, self._pre_host = _PINNED.take(self.device, nblob)
             if self._pre_host is not None:
-                self._pre_host.copy_(self.status[:nblob], non_blocking=True)
+                self._pre_host.copy_((pre if self.K is not None else self.status)[:nblob], non_blocking=True)
                 self._pre_event = torch.cuda.Event()
                 self._pre_event.record(torch.cuda.current_stream(self.device))
         # soft rows: a bad entry of w is the pre-factorisation's QPX_ST_NONFINITE, a bit the loop may set too -- where no
@@ -452,6 +484,12 @@ a non-zero diagonal.
         if bad_entry:
             raise ValueError(bad_entry)
 
+    def _no_groups(self, bad=True, what=None):
+        """scenario groups (build(scenarios=K)) have the loop and the backward: every other launch indexes the blob by QP"""
+        if self.K is not None and bad:
+            raise RuntimeError("qpth_amd: %s is not served on factors built with scenarios=%d (one blob per group of %d QPs); "
+                               "build the factors of the expanded batch instead" % (what, self.K, self.K))
+
     def _no_refine_on_soft(self, refine, what):
         """refinement evaluates residuals from the caller's Q, G, A: of the HARD QP"""
         if self.soft and refine > 0:
@@ -523,6 +561,16 @@ a non-zero diagonal.
         B, n, m, q = self.B, self.n, self.m, self.q
         r = self._new_result(maxIter, want_trace)
         kw = {}
+        if self.K is not None:
+            # scenario groups: the same loop kernel on the B QPs, QP j reading blob j // K
+            self._no_groups(warm is not None, "ipm(warm=...)")
+            self._check_ph(p, h)
+            self._check_b(b)
+            with self._knob():
+                self.lib.ipm_group(self.groups, self.K, n, m, q, p, h, b if q else None, self.blob, self.sfac, eps, maxIter,
+                                   notImprovedLim, self._stall(stall_policy), r.zhat, r.nu if q else None, r.lam, r.slacks,
+                                   r.iters, self.status, r.best_resid, r.trace, wide=self.wide)
+            return r
         if warm is not None:
             lam0, s0 = warm
             if not (warm_floor > 0 and warm_floor < float("inf")):
@@ -547,7 +595,7 @@ a non-zero diagonal.
     def _role_ok(self, symbol):
         """does the role whose qpx_*_supported is `symbol` serve these factors (under the knob they were built with)?  float64
         tensors, the thread-grid / tile kernels' sizes (nz+neq+nineq <= 208), HARD factors"""
-        if self.soft or self.wide or self.dtype != torch.float64 or not hasattr(self.lib.dll, symbol):
+        if self.soft or self.wide or self.K is not None or self.dtype != torch.float64 or not hasattr(self.lib.dll, symbol):
             return False
         with self._knob():
             return bool(getattr(self.lib.dll, symbol)(_lib.QPX_F64, self.n, self.m, self.q))
@@ -810,6 +858,7 @@ a non-zero diagonal.
     def solve_kkt(self, d, rx, rs, rz, ry, refine=0):
         """factor_kkt + solve_kkt; refine > 0: that many steps of iterative refinement on the residual of the original
         KKT system (batch.py:228-270, KKTSolvers.IR_UNOPT) inside the kernel, re-using the factorisation."""
+        self._no_groups(True, "solve_kkt")
         self._no_refine_on_soft(refine, "solve_kkt")
         B, n, m, q = self.B, self.n, self.m, self.q
         dt, dev = self.dtype, self.device
@@ -841,6 +890,7 @@ a non-zero diagonal.
         One launch and one factorisation of T = R + diag(1/d) per QP (qpx_factor_solve_kkt_multi) where the thread-grid /
         tile kernels serve the size and refine == 0.  Otherwise -- the large-QP family (nz+neq+nineq > 208), refine > 0 --
         the same result costs K launches of solve_kkt on slices, each with a factorisation of its own.  No host sync."""
+        self._no_groups(True, "solve_kkt_many")
         self._no_refine_on_soft(refine, "solve_kkt_many")
         B, n, m, q = self.B, self.n, self.m, self.q
         dt, dev = self.dtype, self.device
@@ -884,6 +934,7 @@ a non-zero diagonal.
         / tile kernels serve the size, a stream-ordered sequence of the large-QP family's launches beyond (v7).  No host
         sync.  (Rounds 2-4 composed this stage from torch operations on the host side for the sizes without a kernel;
         that version now lives in tests/polish_reference.py as the step-by-step reference of the kernels.)"""
+        self._no_groups(True, "polish")
         if self.soft:
             raise ValueError("qpth_amd: no finishing stage (qpx_polish: KKTSolvers.IR_UNOPT, float32 refine=k) on factors with "
                              "soft rows (w / rho): its steps evaluate the residuals of the hard QP")
@@ -925,6 +976,7 @@ a non-zero diagonal.
         `res`, its zhat, nu, lam, slacks overwritten, with `centre_resid` (B,) and `centre_steps` int32 (B,) added; a QP that
         ends above tol has _lib.ST_NOT_CENTRED in `res.status`.  backward, jvp, backward2 and solve_kkt_many serve the centred
         point as they stand; d loss / d kappa = dz / lam, dz of backward(want_dz=True)."""
+        self._no_groups(True, "centre")
         if self.soft:
             raise ValueError("qpth_amd: no centring (qpx_centre) on factors with soft rows (w / rho): its steps evaluate the "
                              "residuals of the hard QP")
@@ -953,6 +1005,7 @@ a non-zero diagonal.
         parameter's shape, batched, batch-1 or shared -- at the forward's (zhat, lam, slacks, nu): ONE KKT solve with the
         matrix the backward factors (d = clamp(lam) / clamp(slacks), qp.py:148), its right-hand side formed from the tangents
         inside the kernel (qpx_jvp, include/qpx.h).  Returns z' (B, n); want_duals: (z', lam', nu').  No host sync."""
+        self._no_groups(True, "jvp")
         self._no_refine_on_soft(refine, "jvp")
         B, n, m, q = self.B, self.n, self.m, self.q
         dt, dev = self.dtype, self.device
@@ -992,6 +1045,7 @@ a non-zero diagonal.
         want_sol: a last value behind those, (dx, dz, dy) -- the solution of the backward KKT system as the launch wrote it (dy
         None without equality constraints): what backward2 differentiates through."""
         self._no_refine_on_soft(refine, "backward")
+        self._no_groups(refine > 0, "backward with refine=%d" % refine)
         B, n, m, q = self.B, self.n, self.m, self.q
         want = self._wanted(want)
         grads, (dx, dz, dy) = self._grad_buffers(want, shared, dz_too=want_dz, sol_too=want_sol)
@@ -1001,6 +1055,17 @@ a non-zero diagonal.
         if gz is None and gl is None and gn is None:
             raise RuntimeError("qpth_amd: backward needs at least one of dl_dz, dl_dlam, dl_dnu")
         duals = {} if (gl is None and gn is None and gz is not None) else {"dl_dlam": gl, "dl_dnu": gn}
+        if self.K is not None:
+            # scenario groups: the same backward kernel, QP j reading blob j // K; a per-group matrix's gradient is the sum
+            # over the group's QPs -- one grouped contraction each -- and a shared parameter's the mean over all B QPs as ever
+            with self._knob():
+                self.lib.backward_group(self.groups, self.K, n, m, q, self.blob, self.sfac, zh, lm,
+                                        self._vec(slacks, m, "slacks"), nv, gz, dp, dh, db, self.status, dx, dz, dy,
+                                        wide=self.wide, dl_dlam=gl, dl_dnu=gn)
+                grads = self._group_grads(grads, want, shared, (dx, dz, dy), zh, lm, nv)
+                grads = self._shared_grads(grads, want, shared, (dx, dz, dy), zh, lm, nv)
+            out = tuple(grads) + ((dz,) if want_dz else ())
+            return out + ((dx, dz, dy),) if want_sol else out
         with self._knob():
             self.lib.backward(B, n, m, q, self.blob, self.sfac, zh, lm, self._vec(slacks, m, "slacks"), nv,
                               gz, dQ, dp, dG, dh, dA, db, self.status, dx, dz, dy,
@@ -1029,6 +1094,10 @@ a non-zero diagonal.
         def buf(flag, *shape):
             return torch.empty(*shape, dtype=self.dtype, device=self.device) if flag else None
 
+        if self.K is not None:
+            # scenario groups: the kernel writes no matrix gradient -- a batched matrix's is contracted per group from the KKT
+            # solution (_group_grads), as a shared one's is over the batch
+            sQ, sG, sA = sQ or wQ, sG or wG, sA or wA
         dQ = buf(wQ and not sQ, B, n, n)
         dG = buf(wG and not sG, B, m, n)
         dA = buf(wA and not sA, B, q, n)
@@ -1039,6 +1108,24 @@ a non-zero diagonal.
         dz = buf((wh and sh) or (wG and sG) or dz_too or sol_too, B, m)
         dy = buf(q > 0 and ((wb and sb) or (wA and sA) or sol_too), B, q)
         return [dQ, dp, dG, dh, dA, db], (dx, dz, dy)
+
+    def _group_grads(self, grads, want, shared, sol, zh, lm, nv):
+        """Scenario groups: the gradients of the matrices each GROUP has of its own (wanted, not shared by the batch), (groups,
+        ., .) -- the sum over the group's K QPs of the per-QP outer products (qp.py:167-173), one grouped contraction each
+        (qpx_group_outer), in the order Q, G, A.  Called as _shared_grads is."""
+        n, m, q, G, K = self.n, self.m, self.q, self.groups, self.K
+        dt, dev = self.dtype, self.device
+        dx, dz, dy = sol
+        if want[0] and not shared[0]:
+            grads[0] = torch.empty(G, n, n, dtype=dt, device=dev)
+            self.lib.group_outer(K, dx, zh, zh, dx, 0.5, grads[0])
+        if want[2] and not shared[2]:
+            grads[2] = torch.empty(G, m, n, dtype=dt, device=dev)
+            self.lib.group_outer(K, dz, zh, lm, dx, 1.0, grads[2])
+        if want[4] and not shared[4]:
+            grads[4] = torch.empty(G, q, n, dtype=dt, device=dev)
+            self.lib.group_outer(K, dy, zh, nv, dx, 1.0, grads[4])
+        return grads
 
     def _shared_grads(self, grads, want, shared, sol, zh, lm, nv, lam_lo=None):
         """The gradients of the parameters the batch shares, from the KKT solution `sol` a backward launch wrote: the
@@ -1075,7 +1162,7 @@ a non-zero diagonal.
     # -- the backward of the backward ------------------------------------------------
     def backward2_fused(self):
         """does qpx_backward2 serve these factors (under the knob they were built with)?"""
-        if self.soft or not hasattr(self.lib.dll, "qpx_backward2_supported"):
+        if self.soft or self.K is not None or not hasattr(self.lib.dll, "qpx_backward2_supported"):
             return False
         with self._knob():
             return bool(self.lib.dll.qpx_backward2_supported(self.code, self.n, self.m, self.q))
@@ -1093,6 +1180,7 @@ a non-zero diagonal.
         dl_dnu=): the large-QP family (nz+neq+nineq > 208), float32 kernels, forms the fused entry declines.  True / False
         force one or the other (True raises where the library declines).  Second derivatives of a QP's solution exist only
         under strict complementarity; soft factors and refinement are not served.  No host sync."""
+        self._no_groups(True, "backward2")
         if self.soft:
             raise RuntimeError("qpth_amd: second derivatives are not served on factors with soft rows (w / rho)")
         B, n, m, q = self.B, self.n, self.m, self.q

@@ -28,6 +28,9 @@ QPFunction(...)(Q, p, G, h, A, b, soft_range=SoftRange(lower, l1, rho)) composes
 each side's violation, every row choosing its own kind, in nineq rows and nz variables -- not the augmented dense QP in (z, tu, tl)
 with 4 nineq rows --, differentiable in the five fields: the loop's soft-range role, the range role's backward (qpx_ipm_soft_range,
 DESIGN 4.13).
+QPFunction(scenarios=K)(Q, p, G, h, A, b) solves every (Q, G, A) for K vectors (p, h, b) -- perturbed optimisers, scenario MPC,
+sweeps -- with ONE factorisation per (Q, G, A) and the matrices' gradients summed per group on the matrix cores; the call
+equals the existing one on the expanded batch (qpx_ipm_group).
 """
 from enum import Enum
 
@@ -172,9 +175,24 @@ def f64_arithmetic_serves(nz, nineq, neq, lib=None):
 
 def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
                maxIter=20, solver=QPSolvers.PDIPM_BATCHED,
-               check_Q_spd=True, refine=None, duals=False, warm_start=None, kappa_tol=1e-9, kappa_steps=20):
-    """Returns f(Q, p, G, h, A, b, rho=None, kappa=None, lower=None, l1=None, soft_range=None).  `refine`, `duals`, `warm_start` and the
-    inputs `rho`, `kappa`, `lower`, `l1` and `soft_range` are what the reference does not have.
+               check_Q_spd=True, refine=None, duals=False, warm_start=None, kappa_tol=1e-9, kappa_steps=20, scenarios=None):
+    """Returns f(Q, p, G, h, A, b, rho=None, kappa=None, lower=None, l1=None, soft_range=None).  `refine`, `duals`, `warm_start`,
+    `scenarios` and the inputs `rho`, `kappa`, `lower`, `l1` and `soft_range` are what the reference does not have.
+    scenarios=K: a GROUPED batch -- B different (Q, G, A), each solved for K vectors (p, h, b): K noisy copies of
+      p (perturbed optimisers, randomised smoothing), K disturbance realisations in h, b (scenario / robust MPC), sweeps and
+      multi-starts.  Q, G, A: batched (B, ., .) or un-batched; p, h, b each (B, K, .), (B, .) (shared by that QP's K
+      scenarios) or (.) (shared by all); the outputs are (B, K, .).  The call EQUALS the existing call on the expanded batch of
+      B K QPs -- a batched X as X.repeat_interleave(K, 0), an un-batched X as itself, p, h, b flattened to (B K, .) -- in its
+      values (the forward bit for bit), in every gradient convention (a batched matrix gets the sum over its K scenarios, a
+      (B, .) vector likewise, an un-batched parameter the `.mean(0)` over all B K QPs) and in its errors (a bad Q in one
+      group raises as the expanded call does).  What it saves: K - 1 of every K pre-factorisations and factor blobs, and the
+      B K outer products per matrix gradient that autograd would add up again -- one contraction per group instead.
+      duals=True is served, in reverse mode.  Where the kernels cannot share a blob (qpx_group_supported is 0: the large-QP
+      family, nz + neq + nineq > 208) and for float32 inputs that run with finishing steps, the call builds the expanded
+      batch itself: scenarios= works at every size, there only without the saving.  With Q, G, A all un-batched it is the
+      existing one-blob path on B K QPs.  Not together with rho, kappa, lower, l1, soft_range, warm_start, refine > 0 or
+      solver=QPSolvers.CVXPY: each a ValueError that names the expanded call as the way out.  Forward mode and
+      create_graph=True: RuntimeError.  scenarios=None is the call as before: the same nodes and launches.
     soft_range: SOFT two-sided inequality rows, a qpth_amd.SoftRange(lower, l1, rho, l1_lower=None, rho_lower=None),
           min 1/2 z'Qz + p'z + sum_i ( l1_i tu_i + 1/2 rho_i tu_i^2 + l1_lower_i tl_i + 1/2 rho_lower_i tl_i^2 )
           s.t.  lower - tl <= Gz <= h + tu,  tu, tl >= 0,  Az = b:
@@ -647,6 +665,100 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
             five = tuple(None if g is None else _reduce_like(g, dim) for g, dim in zip(grads[6:], ctx.dims))
             return _without_A_b(grads[:6], ctx.neq) + five
 
+    class QPScenarioFunctionFn(Function):
+        """the node of a grouped batch (scenarios=K): Q_, G_, A_ as the caller gave them -- (B, ., .) or un-batched,
+        at least one batched --, p_, h_, b_ flattened to (B K, .) or un-batched.  One blob per group; the loop and the backward
+        run on B K QPs; a batched matrix's gradient comes back per group, summed over its scenarios."""
+        @staticmethod
+        def forward(ctx, Q_, p_, G_, h_, A_, b_):
+            K = int(scenarios)
+            B = max(X.size(0) for X in (Q_, G_, A_) if X.dim() == 3)
+            nineq, nz, neq = G_.size(-2), G_.size(-1), _neq_of(A_)
+            ctx.neq = neq
+            wide = (refine is None and Q_.dtype == torch.float32
+                    and f64_arithmetic_serves(nz, nineq, neq, _lib.backend_for(Q_)))
+            fac = KKTFactors.build(Q_, G_, A_, B, wide=wide, scenarios=K)
+            res = fac.ipm(p_, h_, b_, eps, maxIter, notImprovedLim, want_trace=(verbose == 1))
+            _loop_epilogue(fac, res, check_Q_spd, verbose)
+            ctx.fac = fac
+            ctx.nus, ctx.lams, ctx.slacks = res.nu.detach(), res.lam.detach(), res.slacks.detach()
+            ctx.save_for_backward(res.zhat, Q_, p_, G_, h_, A_, b_)
+            if not duals:
+                return res.zhat
+            _mark_duals(ctx, neq, res.nu, res.slacks)
+            return res.zhat, res.nu, res.lam, res.slacks
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            raise RuntimeError("qpth_amd: forward mode is not served with scenarios=; call the expanded batch "
+                               "(X.repeat_interleave(K, 0) for batched Q, G, A; p, h, b flattened) without scenarios=")
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dl_dzhat, dl_dnu=None, dl_dlam=None, dl_dslacks=None):
+            zhats, *six = ctx.saved_tensors
+            neq = ctx.neq
+            if dl_dzhat is None and dl_dlam is None and (dl_dnu is None or neq == 0):
+                return (None,) * 6
+            grads = ctx.fac.backward(zhats, ctx.lams, ctx.slacks, ctx.nus, dl_dzhat, want=tuple(ctx.needs_input_grad[:6]),
+                                     shared=_shared_flags(six), dl_dlam=dl_dlam, dl_dnu=dl_dnu if neq > 0 else None)
+            return _without_A_b(tuple(grads), neq)
+
+    _EXPANDED = ("; call the expanded batch without scenarios= instead (X.repeat_interleave(K, 0) for batched Q, G, A; p, h, b "
+                 "flattened to (B K, .))")
+
+    def _apply_scenarios(Q, p, G, h, A, b, extras):
+        """scenarios=K: the refusals, the shapes, then the one-blob path (nothing batched among Q, G, A), the expanded batch (a
+        size or dtype the grouped kernels do not serve) or the grouped node; outputs (B, K, .)"""
+        what = "qpth_amd: scenarios="
+        for name, x in extras:
+            if x is not None:
+                raise ValueError(what + " together with %s is not served" % name + _EXPANDED)
+        if warm_start is not None:
+            raise ValueError(what + " with warm_start is not served" + _EXPANDED)
+        if refine is not None and int(refine) > 0:
+            raise ValueError(what + " with refine=%d is not served: pass refine=0 or refine=None" % int(refine) + _EXPANDED)
+        if solver != QPSolvers.PDIPM_BATCHED:
+            raise ValueError(what + " is served by solver=QPSolvers.PDIPM_BATCHED only" + _EXPANDED)
+        if isinstance(scenarios, bool) or int(scenarios) != scenarios or int(scenarios) < 1:
+            raise ValueError(what + "%r: the number of scenarios per (Q, G, A) must be a positive integer" % (scenarios,))
+        K = int(scenarios)
+        mats, vecs = ((Q, "Q"), (G, "G"), (A, "A")), ((p, "p"), (h, "h"), (b, "b"))
+        sizes = [X.size(0) for X, _ in mats if X.dim() == 3] + [X.size(0) for X, _ in vecs if X.dim() in (2, 3)]
+        B = sizes[0] if sizes else 1
+        for X, name in mats:
+            if X.nelement() > 0 and (X.dim() not in (2, 3) or (X.dim() == 3 and X.size(0) != B)):
+                raise ValueError(what + "%d: %s has shape %s; expected (%d, ., .) or un-batched" % (K, name, tuple(X.shape), B))
+        flat = []
+        for X, name in vecs:
+            if X.nelement() > 0:
+                if X.dim() not in (1, 2, 3) or (X.dim() >= 2 and X.size(0) != B) or (X.dim() == 3 and X.size(1) != K):
+                    raise ValueError(what + "%d: %s has shape %s; expected (%d, %d, .), (%d, .) or (.)"
+                                     % (K, name, tuple(X.shape), B, K, B))
+                if X.dim() == 2:              # shared by that QP's scenarios: materialised (small), autograd sums over them
+                    X = X.unsqueeze(1).expand(B, K, X.size(-1))
+                if X.dim() == 3:
+                    X = X.reshape(B * K, X.size(-1))
+            flat.append(X)
+        p, h, b = flat
+        batched = [X.dim() == 3 for X, _ in mats]
+        if not any(batched):
+            out = QPFunctionFn.apply(Q, p, G, h, A, b)                # one blob for all B K QPs, as without scenarios=
+        else:
+            lib = _lib.backend_for(Q)
+            nineq, nz, neq = G.size(-2), G.size(-1), _neq_of(A)
+            wide = refine is None and Q.dtype == torch.float32 and f64_arithmetic_serves(nz, nineq, neq, lib)
+            code = _lib.QPX_F32_WIDE if wide else _lib._dtype_code(Q)
+            finishing = Q.dtype == torch.float32 and refine is None and not wide       # (float32 kernels + finishing steps: per-QP data)
+            if finishing or not lib.group_supported(code, nz, nineq, neq):
+                Q, G, A = [X.repeat_interleave(K, 0) if X.dim() == 3 else X for X, _ in mats]
+                out = QPFunctionFn.apply(Q, p, G, h, A, b)            # the expanded batch itself: no saving, the same answer
+            else:
+                out = QPScenarioFunctionFn.apply(Q, p, G, h, A, b)
+        if torch.is_tensor(out):
+            return out.reshape(B, K, out.size(-1)) if out.size(0) == B * K else out.unsqueeze(1).expand(B, K, out.size(-1))
+        return tuple(X.reshape(B, K, X.size(-1)) if X.size(0) == B * K else X.unsqueeze(1).expand(B, K, X.size(-1)) for X in out)
+
     # the options of this QPFunction(...) that a row kind may refuse (_ROW_KINDS): is each one set?
     # (a RangeWarmStart is the range role's own holder: apply() has refused it everywhere else, the role does not refuse it)
     range_ws = isinstance(warm_start, RangeWarmStart)
@@ -670,6 +782,9 @@ def QPFunction(eps=1e-12, verbose=0, notImprovedLim=3,
 
     def apply(Q, p, G, h, A, b, rho=None, kappa=None, lower=None, l1=None, soft_range=None):
         nineq = G.size(-2)
+        if scenarios is not None:
+            return _apply_scenarios(Q, p, G, h, A, b, (("rho", rho), ("kappa", kappa), ("lower", lower), ("l1", l1),
+                                                       ("soft_range", soft_range)))
         if range_ws:
             with_ = [name for name, x in (("rho", rho), ("kappa", kappa), ("l1", l1), ("soft_range", soft_range)) if x is not None]
             if lower is None or with_:
